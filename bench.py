@@ -77,6 +77,7 @@ class Pipeline:
         self.gather_buf = torch.empty(int(cap * world * 0.75) + 1024, dtype=torch.uint8, device=dev) if (world > 1 and rank == 0) else None
         self.pending = None
         self.ncall = 0
+        self.last_out = None  # (records, plane_bytes, decoded words) of the last codec call of the last step
 
     def finish_gather(self):
         """the previous call's concatenation must be complete (on the device) before its buffers are reused"""
@@ -108,6 +109,7 @@ class Pipeline:
             td += t2 - t1
             zbytes += rec.numel()
             last = (rec, planes)
+            self.last_out = (rec, planes, out)
             if verify:  # bit-exact round trip == erasebytes(input), batch by batch (outside the timed region)
                 exp = sub.clone()
                 self.codec.erase_bits_device(exp, self.bits, self.f_lo + b * self.bfl)
@@ -252,6 +254,29 @@ def parity_check(words_dev, rec, bits, nchunks):
         return f"not run: {str(e)[:120]}"
 
 
+DUMP_SAMPLE = 4 * 1048576  # elements kept per dumped array: 2 x 16 MB of float32, well under the 64 MB budget
+DUMP_SEED = 20240917
+
+
+def dump_outputs(d, rec, planes, out, torch):
+    """--dump-outputs: what the timed path handed its caller in the last call of the last timed step, as float32 / float64
+    .npy files -- the decoded words (float32 bit patterns, i.e. erasebytes(input)), the chunk-record bytes (values 0..255)
+    and the plane byte counts.  Arrays longer than DUMP_SAMPLE are sampled at the same seeded, sorted positions every run."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+
+    def sample(t):
+        n = t.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        return t.cpu().numpy()
+
+    np.save(os.path.join(d, "decoded_words.npy"), sample(out).view(np.float32))
+    np.save(os.path.join(d, "records.npy"), sample(rec).astype(np.float32))
+    np.save(os.path.join(d, "plane_bytes.npy"), np.array([rec.numel()] + list(planes), np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -261,7 +286,10 @@ def main():
     ap.add_argument("--gib-per-gpu", type=float, default=1.0)
     ap.add_argument("--stream", action="store_true", help="streaming mode (device-generated App. D volume, batches of 128 chunks); implied above 4 GiB")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write (a fixed, seeded sample of) the last timed step's outputs as .npy files into DIR")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     from datacompressionfloat_amd import MrcZipCodec, shard
@@ -305,6 +333,8 @@ def main():
     if dist is not None:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     elapsed, tc, td = tt.tolist()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *pipe.last_out, torch)
 
     # ---- bit-exact round trip check: one more, untimed, pass ----
     _, _, zbytes, ok, last = pipe.step(verify=True)

@@ -22,8 +22,7 @@ import util  # noqa: E402
 
 import numpy as np  # noqa: E402
 
-REF = util.ref_binary("mrc_tar_c")
-assert REF, "oracle/_ref/mrc_tar_c missing: run `make -C oracle ref` in the build container"
+REF = None  # oracle/_ref/mrc_tar_c, looked up by main(): the case lists above main() are imported by the tests without it
 
 SURVEY_D = {  # SURVEY.md Appendix D (reference + zlib 1.2.8): name -> {bits: (size, sha256 or 16-hex prefix)}
     "katA": {0: (769630, "c69720170255cb16341c414bc6ebb557bf65f708bc889b7f00b7e73ea8cec4b5"),
@@ -123,6 +122,9 @@ def small_cases():
 
 
 def main():
+    global REF
+    REF = util.ref_binary("mrc_tar_c")
+    assert REF, "oracle/_ref/mrc_tar_c missing: run `make -C oracle ref` in the build container"
     golden = {"survey_appendix_d": {k: {str(b): list(v) for b, v in d.items()} for k, d in SURVEY_D.items()},
               "kat_inputs": {"katA": 300000, "katB": 6303801}, "regenerated": {}, "small": {}, "large": {}}
     for name, n in golden["kat_inputs"].items():
