@@ -9,6 +9,7 @@ importing :mod:`datacompressionfloat_amd.codec` raises if the HIP library is mis
 from .codec import (  # noqa: F401
     CHUNK_FLOATS,
     FILE_HEADER_BYTES,
+    MRC_HEADER_BYTES,
     MrcZipCodec,
     MrczError,
     pack_file_header,

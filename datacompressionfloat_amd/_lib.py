@@ -37,6 +37,12 @@ def load():
     lib.mrcz_compress_chunks_int8.argtypes = [vp, vp, u64, u64, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.mrcz_uncompress_chunks_int8.restype = i32
     lib.mrcz_uncompress_chunks_int8.argtypes = [vp, vp, u64, u64, u32, u64, vp, ctypes.POINTER(u64)]
+    lib.mrcz_record_size.restype = i32
+    lib.mrcz_record_size.argtypes = [vp, u32, ctypes.POINTER(u64)]
+    lib.mrcz_records_index.restype = i32
+    lib.mrcz_records_index.argtypes = [vp, u64, u64, u32, ctypes.POINTER(u64)]
+    lib.mrcz_uncompress_range.restype = i32
+    lib.mrcz_uncompress_range.argtypes = [vp, vp, u64, u64, u32, u64, u64, u64, vp, i32, ctypes.POINTER(u64)]
     lib.mrcz_generate_kat_words.restype = i32
     lib.mrcz_generate_kat_words.argtypes = [vp, vp, u64, u64]
     lib.mrcz_set_ztypes.restype = i32
@@ -63,4 +69,5 @@ EXPORTS = [
     "mrcz_event_create", "mrcz_event_destroy", "mrcz_event_record", "mrcz_stream_wait_event", "mrcz_event_sync",
     "mrcz_copy_h2d_async", "mrcz_copy_d2h_async", "mrcz_compress_chunks_async", "mrcz_uncompress_chunks_async",
     "mrcz_set_ztypes", "mrcz_generate_kat_words", "mrcz_err_hist", "mrcz_err_collect", "mrcz_compress_chunks_int8", "mrcz_uncompress_chunks_int8", "mrcz_compress_chunks_int8_async", "mrcz_uncompress_chunks_int8_async",
+    "mrcz_record_size", "mrcz_records_index", "mrcz_uncompress_range", "mrcz_uncompress_range_async",
 ]

@@ -6,6 +6,8 @@ header I/O of src/core/common.c:117-148 with the same argument meaning: `bits` i
 Device memory comes from torch; all arithmetic happens in libmrcz_hip.so.
 """
 import ctypes
+import io
+import os
 import struct
 
 import torch
@@ -14,6 +16,7 @@ from . import _lib
 
 CHUNK_FLOATS = 6 * 1048576  # src/include/constant.h:25
 FILE_HEADER_BYTES = 17      # src/core/common.c:137-148
+MRC_HEADER_BYTES = 1024     # MRC2014: the fixed header before the extended header (nsymbt bytes) and the data
 
 _LIB = _lib.load()  # raises MrczLibraryMissing: no CPU fallback
 
@@ -121,6 +124,24 @@ class MrcZipCodec:
             raise self._err("mrcz_uncompress_chunks", rc)
         return out[:nfloats], int(consumed.value)
 
+    def uncompress_range_device(self, records: torch.Tensor, nfloats_file: int, w0: int, w1: int, chk: int = CHUNK_FLOATS,
+                                first_chunk: int = 0, out: torch.Tensor = None, int_mode: bool = False):
+        """words [w0, w1) of a file of nfloats_file floats.  `records` (cuda uint8) = the chunk records of chunks first_chunk,
+        first_chunk + 1, ... (first_chunk <= w0 // chk; records before the window's first chunk are only walked).  Only the
+        chunks that cover the window are decoded.  Returns (words int32 cuda tensor, record bytes consumed)."""
+        assert records.is_cuda and records.dtype == torch.uint8 and records.is_contiguous()
+        n = w1 - w0
+        if out is None:
+            out = torch.empty(max(n, 1), dtype=torch.int32, device=records.device)
+        assert out.is_cuda and out.numel() >= n and out.element_size() == 4
+        torch.cuda.current_stream(records.device).synchronize()
+        consumed = ctypes.c_uint64()
+        rc = _LIB.mrcz_uncompress_range(self._ctx, records.data_ptr(), records.numel(), nfloats_file, chk, first_chunk, w0, w1,
+                                        out.data_ptr(), 1 if int_mode else 0, ctypes.byref(consumed))
+        if rc != 0:
+            raise self._err("mrcz_uncompress_range", rc)
+        return out[:n], int(consumed.value)
+
     def erase_bits_device(self, words: torch.Tensor, bits: int, first_word_index: int = 0):
         assert words.is_cuda and words.element_size() == 4
         torch.cuda.current_stream(words.device).synchronize()
@@ -171,3 +192,76 @@ class MrcZipCodec:
         rec = torch.frombuffer(bytearray(container[FILE_HEADER_BYTES:]), dtype=torch.uint8).to(self.device)
         out, _ = self.uncompress_device(rec, nfl, chk, int_mode=(mode == "int"))
         return out.cpu().numpy().tobytes()
+
+    # ---- range decode: part of a container without reading or decoding the rest ----
+    def _range_device(self, f, w0: int, w1: int, mode: str) -> torch.Tensor:
+        """words [w0, w1) of the container open as binary file `f`: reads the file header, the 16-byte headers of the chunks
+        before the window and the records of the chunks that cover it, nothing else"""
+        if mode not in ("float", "int"):
+            raise MrczError("mode must be 'float' or 'int' (mrc_tar -s)")
+        f.seek(0)
+        fsz, chk, typ, ztypes = unpack_file_header(f.read(FILE_HEADER_BYTES))
+        if any(z not in (0, 2, 4) for z in ztypes):
+            raise MrczError("byte stream compressor types must be ZLIB_DEF (0), LZ4_DEF (2) or LZ4HC_DEF (4)")
+        if chk == 0:
+            raise MrczError("chunk size 0 in header (the reference divides by it, src/core/workers.c:589)")
+        nfl = fsz // 4
+        if not 0 <= w0 < w1 <= nfl:
+            raise MrczError(f"window [{w0}, {w1}) is empty or outside the file's {nfl} words")
+        rc = _LIB.mrcz_set_ztypes(self._ctx, bytes(bytearray(z & 0xff for z in ztypes)))
+        if rc != 0:
+            raise self._err("mrcz_set_ztypes", rc)
+        c_lo, c_hi = w0 // chk, (w1 + chk - 1) // chk
+        off, start, size = FILE_HEADER_BYTES, 0, ctypes.c_uint64()
+        for c in range(c_hi):
+            if c == c_lo:
+                start = off
+            f.seek(off)
+            h = f.read(16)
+            if len(h) < 16 or _LIB.mrcz_record_size(h, min(chk, nfl - c * chk), ctypes.byref(size)) != 0:
+                raise MrczError(f"damaged or truncated container: chunk header {c} at byte {off}")
+            off += size.value
+        f.seek(start)
+        body = f.read(off - start)
+        if len(body) != off - start:
+            raise MrczError("truncated container: the records of the window end early")
+        rec = torch.frombuffer(bytearray(body), dtype=torch.uint8).to(self.device)
+        out, _ = self.uncompress_range_device(rec, nfl, w0, w1, chk, first_chunk=c_lo, int_mode=(mode == "int"))
+        return out
+
+    def _open(self, container_or_path):
+        if isinstance(container_or_path, (bytes, bytearray, memoryview)):
+            return io.BytesIO(container_or_path)
+        return open(os.fspath(container_or_path), "rb")
+
+    def unzip_range(self, container_or_path, w0: int, w1: int, mode: str = "float") -> bytes:
+        """bytes 4*w0 .. 4*w1 of what unzip_bytes returns, from a container in memory or a path; for a path only the covering
+        chunk records are read from the file."""
+        with self._open(container_or_path) as f:
+            return self._range_device(f, w0, w1, mode).cpu().numpy().tobytes()
+
+    def read_mrc_slab(self, path, z0: int, z1: int) -> torch.Tensor:
+        """sections [z0, z1) of a compressed float32 (mode 2) MRC volume as a (z1 - z0, ny, nx) float32 cuda tensor.  The MRC
+        header (nx, ny, nz, mode at bytes 0-15, nsymbt at 92-95) comes from the decoded first 256 words; the data start at
+        byte 1024 + nsymbt."""
+        with self._open(path) as f:
+            f.seek(0)
+            fsz = unpack_file_header(f.read(FILE_HEADER_BYTES))[0]
+            if fsz // 4 < MRC_HEADER_BYTES // 4:
+                raise MrczError("file shorter than an MRC header")
+            hdr = self._range_device(f, 0, MRC_HEADER_BYTES // 4, "float").cpu().numpy().tobytes()
+            nx, ny, nz, mode = struct.unpack("<4i", hdr[:16])
+            (nsymbt,) = struct.unpack("<i", hdr[92:96])
+            if mode != 2:
+                raise MrczError(f"MRC mode {mode}: only mode 2 (float32) volumes can be read as slabs")
+            if nx <= 0 or ny <= 0 or nz <= 0 or nsymbt < 0 or nsymbt % 4:
+                raise MrczError(f"implausible MRC header: nx={nx} ny={ny} nz={nz} nsymbt={nsymbt}")
+            if not 0 <= z0 < z1 <= nz:
+                raise MrczError(f"sections [{z0}, {z1}) outside 0..{nz}")
+            sec = nx * ny
+            w0 = (MRC_HEADER_BYTES + nsymbt) // 4 + z0 * sec
+            w1 = w0 + (z1 - z0) * sec
+            if w1 > fsz // 4:
+                raise MrczError("the MRC header describes more data than the file holds")
+            out = self._range_device(f, w0, w1, "float")
+        return out.view(torch.float32).reshape(z1 - z0, ny, nx)

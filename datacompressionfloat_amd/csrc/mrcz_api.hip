@@ -534,19 +534,13 @@ extern "C" int mrcz_compress_chunks_async(mrcz_ctx_t *ctx, const void *d_in, uin
     return compress_enqueue(ctx, d_in, nfloats, first_chunk, bits, d_out, out_cap, h_result5, 0);
 }
 
-/* enqueue an uncompress call; its three result words (record bytes consumed, error count, streams handed to the sequential
- * decoder) are copied to the pinned host words h_res[0..2] in stream order.  No host synchronisation. */
-static int uncompress_enqueue(mrcz_ctx_t *ctx, const void *d_records, uint64_t len, uint64_t nfloats, uint32_t chk, void *d_out, uint64_t *h_res,
-                              int int_mode, uint64_t first_chunk)
+/* what every uncompress call checks and allocates before its first batch */
+static int uncompress_prepare(mrcz_ctx_t *ctx, const void *d_records, uint32_t chk, void *d_out)
 {
-    if (!ctx || !d_out || !h_res) return MRCZ_EINVAL;
-    ctx->ntimers = 0;
-    if (nfloats == 0) return fail(ctx, MRCZ_EINVAL, "nothing to uncompress", hipSuccess);
     if (!d_records) return MRCZ_EINVAL;
     if (chk == 0 || chk > CHK) return fail(ctx, MRCZ_EFORMAT, "chunk size in header exceeds CHUNK_SIZE (constant.h:25)", hipSuccess);
     if (((uintptr_t)d_out & 15u) || ((uintptr_t)d_records & 3u)) return fail(ctx, MRCZ_EINVAL, "d_out must be 16-byte and d_records 4-byte aligned", hipSuccess);
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
-    hipStream_t lstream = ctx->stream;
     if (int rc = ensure_planes(ctx)) return rc;
     if (!ctx->scratch) {
         /* real blocks fill at most the planes' size; false candidates and 16-byte rounding get another half */
@@ -560,6 +554,60 @@ static int uncompress_enqueue(mrcz_ctx_t *ctx, const void *d_records, uint64_t l
         hipError_t e = hipMalloc((void **)&ctx->scratch, (size_t)ctx->scratch_bytes + 32u);
         if (e != hipSuccess) { ctx->scratch = NULL; return fail(ctx, MRCZ_ENOMEM, "decode scratch", e); }
     }
+    return MRCZ_OK;
+}
+
+/* parse the records of one batch of nb chunks (bfl floats) where the previous batch stopped (ctx->result[0]) and decode their
+ * planes into the workspace; the merge is left to the caller */
+static int decode_batch(mrcz_ctx_t *ctx, const uint8_t *rec, uint64_t len, uint64_t bfl, uint32_t nb, uint32_t chk)
+{
+    hipStream_t lstream = ctx->stream;
+    LAUNCH("k_parse_records", k_parse_records, dim3(1), dim3(64), rec, len, bfl, chk, ctx->dstreams, ctx->result, ctx->lz4_planes);
+    const uint32_t ns = 4 * nb;
+    HIPCHK(hipMemsetAsync(ctx->ncand, 0, ns * sizeof(uint32_t), ctx->stream), "memset ncand");
+    HIPCHK(hipMemsetAsync(ctx->njobs, 0, (4 + RAW_SEGS) * sizeof(uint32_t), ctx->stream), "memset njobs");
+    if (ctx->phase_profile == 2 || ctx->phase_profile == 4) HIPCHK(hipMemsetAsync(ctx->dbgphase, 0, (size_t)ns * 40 * sizeof(unsigned long long), ctx->stream), "memset dbg");
+    if (ctx->phase_profile != 1) { /* (1 = profiling vehicle: every stream through the sequential-chain kernel with phase counters) */
+        /* block-parallel path: find block starts, size every candidate block, close the chains, write */
+        ctx->calltag = ctx->calltag * 0x01000193u + 0x9e3779b9u;
+        if (ns <= 48u)
+            LAUNCH("k_scan_candidates", k_scan_candidates<SLAB_BYTES_SMALL>, dim3((CHK + (CHK >> 3) + SLAB_BYTES_SMALL - 1) / SLAB_BYTES_SMALL, ns), dim3(64), rec, len,
+                   ctx->dstreams, ctx->cands, ctx->ncand, ctx->rawlist, ctx->njobs + 4, ctx->rawcap);
+        else
+            LAUNCH("k_scan_candidates", k_scan_candidates<SLAB_BYTES>, dim3((CHK + (CHK >> 3) + SLAB_BYTES - 1) / SLAB_BYTES, ns), dim3(64), rec, len,
+                   ctx->dstreams, ctx->cands, ctx->ncand, ctx->rawlist, ctx->njobs + 4, ctx->rawcap);
+        if (ctx->validate_wave) /* ~280 signature survivors per stream; the more waves in flight, the better their memory round trips overlap (1 GiB: 2048 waves 279 us, 8192 159, 32768 128) */
+            LAUNCH("k_validate_candidates", k_validate_wave, dim3(ctx->validate_grid ? ctx->validate_grid : (ns * 192u < 4096u ? 4096u : ns * 192u > 32768u ? 32768u : ns * 192u)), dim3(64), rec, len, ctx->dstreams, ctx->rawlist, ctx->njobs + 4,
+                   ctx->rawcap, ctx->cands, ctx->ncand, ctx->hdrs, ctx->calltag);
+        else
+            LAUNCH("k_validate_candidates", k_validate_candidates, dim3(2048), dim3(64), rec, len, ctx->dstreams, ctx->rawlist, ctx->njobs + 4,
+                   ctx->rawcap, ctx->cands, ctx->ncand, ctx->hdrs, ctx->calltag,
+                   ctx->phase_profile == 4 ? ctx->dbgphase + (size_t)ns * 8 : (unsigned long long *)NULL);
+        LAUNCH("k_cand_index", k_cand_index, dim3(1), dim3(256), ctx->ncand, ctx->dstreams, ns, ctx->candbase, ctx->jobord);
+        /* fixed grid: the workgroups pull candidate numbers from ctx->njobs[0] until it passes candbase[ns] (no read-back) */
+        LAUNCH("k_blk_count", k_blk_count, dim3(ctx->blk_grid), dim3(PT), rec, len, ctx->dstreams, ns, ctx->candbase, ctx->jobord,
+                 ctx->cands, ctx->scratch + 16, ctx->njobs + 2, (uint32_t)(ctx->scratch_bytes >> 4), ctx->hdrs, ctx->calltag, ctx->njobs,
+                 ctx->phase_profile == 2 ? ctx->dbgphase : (unsigned long long *)NULL, ctx->use_hint);
+    }
+    LAUNCH("k_chain", k_chain, dim3(ns), dim3(64), rec, len, ctx->dstreams, ctx->cands, ctx->ncand, ctx->segs, ctx->nseg, ctx->segidx,
+           ctx->fallback, ctx->phase_profile == 1 ? 1u : 0u, ctx->phase_profile == 4 ? ctx->dbgphase : (unsigned long long *)NULL);
+    LAUNCH("k_inflate_par", k_inflate_par, dim3(ns), dim3(PT), rec, len, ctx->dstreams, ctx->planes, ctx->fallback,
+             ctx->fallback, ctx->phase_profile == 1 ? ctx->dbgphase : (unsigned long long *)NULL, ctx->result);
+    LAUNCH("k_inflate_seq", k_inflate, dim3(ns), dim3(64), rec, ctx->dstreams, ctx->planes, ctx->result, ctx->fallback);
+    if (ctx->lz4_planes) LAUNCH("k_lz4_blocks", k_lz4_blocks, dim3(ns), dim3(64), rec, ctx->dstreams, ctx->planes, ctx->result);
+    return MRCZ_OK;
+}
+
+/* enqueue an uncompress call; its three result words (record bytes consumed, error count, streams handed to the sequential
+ * decoder) are copied to the pinned host words h_res[0..2] in stream order.  No host synchronisation. */
+static int uncompress_enqueue(mrcz_ctx_t *ctx, const void *d_records, uint64_t len, uint64_t nfloats, uint32_t chk, void *d_out, uint64_t *h_res,
+                              int int_mode, uint64_t first_chunk)
+{
+    if (!ctx || !d_out || !h_res) return MRCZ_EINVAL;
+    ctx->ntimers = 0;
+    if (nfloats == 0) return fail(ctx, MRCZ_EINVAL, "nothing to uncompress", hipSuccess);
+    if (int rc = uncompress_prepare(ctx, d_records, chk, d_out)) return rc;
+    hipStream_t lstream = ctx->stream;
     const uint8_t *rec = (const uint8_t *)d_records;
     uint32_t *out = (uint32_t *)d_out;
     const uint64_t nchunks = (nfloats + chk - 1) / chk;
@@ -567,41 +615,9 @@ static int uncompress_enqueue(mrcz_ctx_t *ctx, const void *d_records, uint64_t l
     for (uint64_t c0 = 0; c0 < nchunks; c0 += ctx->max_chunks) {
         const uint32_t nb = (uint32_t)((nchunks - c0) < ctx->max_chunks ? (nchunks - c0) : ctx->max_chunks);
         const uint64_t bfl = (nfloats - c0 * chk) < (uint64_t)nb * chk ? (nfloats - c0 * chk) : (uint64_t)nb * chk;
-        LAUNCH("k_parse_records", k_parse_records, dim3(1), dim3(64), rec, len, bfl, chk, ctx->dstreams, ctx->result, ctx->lz4_planes);
-        const uint32_t ns = 4 * nb;
-        HIPCHK(hipMemsetAsync(ctx->ncand, 0, ns * sizeof(uint32_t), ctx->stream), "memset ncand");
-        HIPCHK(hipMemsetAsync(ctx->njobs, 0, (4 + RAW_SEGS) * sizeof(uint32_t), ctx->stream), "memset njobs");
-        if (ctx->phase_profile == 2 || ctx->phase_profile == 4) HIPCHK(hipMemsetAsync(ctx->dbgphase, 0, (size_t)ns * 40 * sizeof(unsigned long long), ctx->stream), "memset dbg");
-        if (ctx->phase_profile != 1) { /* (1 = profiling vehicle: every stream through the sequential-chain kernel with phase counters) */
-            /* block-parallel path: find block starts, size every candidate block, close the chains, write */
-            ctx->calltag = ctx->calltag * 0x01000193u + 0x9e3779b9u;
-            if (ns <= 48u)
-                LAUNCH("k_scan_candidates", k_scan_candidates<SLAB_BYTES_SMALL>, dim3((CHK + (CHK >> 3) + SLAB_BYTES_SMALL - 1) / SLAB_BYTES_SMALL, ns), dim3(64), rec, len,
-                       ctx->dstreams, ctx->cands, ctx->ncand, ctx->rawlist, ctx->njobs + 4, ctx->rawcap);
-            else
-                LAUNCH("k_scan_candidates", k_scan_candidates<SLAB_BYTES>, dim3((CHK + (CHK >> 3) + SLAB_BYTES - 1) / SLAB_BYTES, ns), dim3(64), rec, len,
-                       ctx->dstreams, ctx->cands, ctx->ncand, ctx->rawlist, ctx->njobs + 4, ctx->rawcap);
-            if (ctx->validate_wave) /* ~280 signature survivors per stream; the more waves in flight, the better their memory round trips overlap (1 GiB: 2048 waves 279 us, 8192 159, 32768 128) */
-                LAUNCH("k_validate_candidates", k_validate_wave, dim3(ctx->validate_grid ? ctx->validate_grid : (ns * 192u < 4096u ? 4096u : ns * 192u > 32768u ? 32768u : ns * 192u)), dim3(64), rec, len, ctx->dstreams, ctx->rawlist, ctx->njobs + 4,
-                       ctx->rawcap, ctx->cands, ctx->ncand, ctx->hdrs, ctx->calltag);
-            else
-                LAUNCH("k_validate_candidates", k_validate_candidates, dim3(2048), dim3(64), rec, len, ctx->dstreams, ctx->rawlist, ctx->njobs + 4,
-                       ctx->rawcap, ctx->cands, ctx->ncand, ctx->hdrs, ctx->calltag,
-                       ctx->phase_profile == 4 ? ctx->dbgphase + (size_t)ns * 8 : (unsigned long long *)NULL);
-            LAUNCH("k_cand_index", k_cand_index, dim3(1), dim3(256), ctx->ncand, ctx->dstreams, ns, ctx->candbase, ctx->jobord);
-            /* fixed grid: the workgroups pull candidate numbers from ctx->njobs[0] until it passes candbase[ns] (no read-back) */
-            LAUNCH("k_blk_count", k_blk_count, dim3(ctx->blk_grid), dim3(PT), rec, len, ctx->dstreams, ns, ctx->candbase, ctx->jobord,
-                     ctx->cands, ctx->scratch + 16, ctx->njobs + 2, (uint32_t)(ctx->scratch_bytes >> 4), ctx->hdrs, ctx->calltag, ctx->njobs,
-                     ctx->phase_profile == 2 ? ctx->dbgphase : (unsigned long long *)NULL, ctx->use_hint);
-        }
-        LAUNCH("k_chain", k_chain, dim3(ns), dim3(64), rec, len, ctx->dstreams, ctx->cands, ctx->ncand, ctx->segs, ctx->nseg, ctx->segidx,
-               ctx->fallback, ctx->phase_profile == 1 ? 1u : 0u, ctx->phase_profile == 4 ? ctx->dbgphase : (unsigned long long *)NULL);
-        LAUNCH("k_inflate_par", k_inflate_par, dim3(ns), dim3(PT), rec, len, ctx->dstreams, ctx->planes, ctx->fallback,
-                 ctx->fallback, ctx->phase_profile == 1 ? ctx->dbgphase : (unsigned long long *)NULL, ctx->result);
-        LAUNCH("k_inflate_seq", k_inflate, dim3(ns), dim3(64), rec, ctx->dstreams, ctx->planes, ctx->result, ctx->fallback);
-        if (ctx->lz4_planes) LAUNCH("k_lz4_blocks", k_lz4_blocks, dim3(ns), dim3(64), rec, ctx->dstreams, ctx->planes, ctx->result);
-        LAUNCH("k_merge_segments", k_merge_segments, dim3(512, nb), dim3(256), rec, ctx->scratch + 16, ctx->planes, ctx->segs, ctx->nseg, ctx->segidx, bfl,
-               chk, out + c0 * chk, len, (uint64_t)4 * ctx->row_chunks * CHK, int_mode ? 1u : 0u, (first_chunk + c0) * (uint64_t)chk);
+        if (int rc = decode_batch(ctx, rec, len, bfl, nb, chk)) return rc;
+        LAUNCH("k_merge_segments", k_merge_segments<false>, dim3(512, nb), dim3(256), rec, ctx->scratch + 16, ctx->planes, ctx->segs, ctx->nseg, ctx->segidx, bfl,
+               chk, out + c0 * chk, len, (uint64_t)4 * ctx->row_chunks * CHK, int_mode ? 1u : 0u, (first_chunk + c0) * (uint64_t)chk, (int64_t)0, (uint64_t)0);
     }
     HIPCHK(hipMemcpyAsync(h_res, ctx->result, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream), "copy result");
     return MRCZ_OK;
@@ -649,6 +665,99 @@ extern "C" int mrcz_uncompress_chunks_int8_async(mrcz_ctx_t *ctx, const void *d_
                                                  uint64_t first_chunk, void *d_out, uint64_t *h_result3)
 {
     return uncompress_enqueue(ctx, d_records, len, nfloats, chk, d_out, h_result3, 1, first_chunk);
+}
+
+/* ---- range decode: words [w0, w1) of a file out of the records of the chunks that cover them ---- */
+
+/* bytes of the chunk record whose 16-byte header is h (payloads included) for a chunk of n floats; the same checks as
+ * k_parse_records (unpack_header, zip.c:393-399) */
+extern "C" int mrcz_record_size(const void *h_header16, uint32_t n, uint64_t *bytes)
+{
+    if (!h_header16 || !bytes) return MRCZ_EINVAL;
+    const uint8_t *h = (const uint8_t *)h_header16;
+    uint64_t tot = 16;
+    for (int j = 0; j < 4; j++) {
+        const uint32_t raw = h[4 * j + 3] >> 7;
+        const uint32_t l = (uint32_t)h[4 * j] | ((uint32_t)h[4 * j + 1] << 8) | ((uint32_t)h[4 * j + 2] << 16) | ((uint32_t)(h[4 * j + 3] & 0x7fu) << 24);
+        if ((raw && l < n) || (!raw && l > CHK + (CHK >> 3) + 1024u)) return MRCZ_EFORMAT;
+        tot += l;
+    }
+    *bytes = tot;
+    return MRCZ_OK;
+}
+
+extern "C" int mrcz_records_index(const void *h_records, uint64_t len, uint64_t nfloats, uint32_t chk, uint64_t *offsets)
+{
+    if (!h_records || !offsets || nfloats == 0) return MRCZ_EINVAL;
+    if (chk == 0 || chk > CHK) return MRCZ_EFORMAT;
+    const uint8_t *rec = (const uint8_t *)h_records;
+    const uint64_t nchunks = (nfloats + chk - 1) / chk;
+    uint64_t off = 0;
+    for (uint64_t c = 0; c < nchunks; c++) {
+        const uint64_t left = nfloats - c * chk;
+        uint64_t b = 0;
+        if (off + 16 > len) return MRCZ_EFORMAT;
+        if (int rc = mrcz_record_size(rec + off, (uint32_t)(left < chk ? left : chk), &b)) return rc;
+        if (b > len - off) return MRCZ_EFORMAT;
+        offsets[c] = off;
+        off += b;
+    }
+    offsets[nchunks] = off;
+    return MRCZ_OK;
+}
+
+static int uncompress_range_enqueue(mrcz_ctx_t *ctx, const void *d_records, uint64_t len, uint64_t nfloats_file, uint32_t chk,
+                                    uint64_t first_chunk, uint64_t w0, uint64_t w1, void *d_out, uint64_t *h_res, int int_mode)
+{
+    if (!ctx || !d_out || !h_res) return MRCZ_EINVAL;
+    ctx->ntimers = 0;
+    if (int rc = uncompress_prepare(ctx, d_records, chk, d_out)) return rc;
+    if (w0 >= w1 || w1 > nfloats_file) return fail(ctx, MRCZ_EINVAL, "window [w0, w1) empty or past the end of the file", hipSuccess);
+    if (first_chunk > w0 / chk) return fail(ctx, MRCZ_EINVAL, "the records begin after the window's first word", hipSuccess);
+    hipStream_t lstream = ctx->stream;
+    const uint8_t *rec = (const uint8_t *)d_records;
+    uint32_t *out = (uint32_t *)d_out;
+    const uint64_t c_lo = w0 / chk, c_hi = (w1 + chk - 1) / chk; /* chunks [c_lo, c_hi) cover the window */
+    HIPCHK(hipMemsetAsync(ctx->result, 0, 8 * sizeof(uint64_t), ctx->stream), "memset result");
+    /* records of chunks before the window: headers walked, nothing decoded (all of them are whole chunks) */
+    for (uint64_t c = first_chunk; c < c_lo; c += ctx->max_chunks) {
+        const uint64_t nb = (c_lo - c) < ctx->max_chunks ? (c_lo - c) : ctx->max_chunks;
+        LAUNCH("k_parse_records", k_parse_records, dim3(1), dim3(64), rec, len, nb * chk, chk, ctx->dstreams, ctx->result, ctx->lz4_planes);
+    }
+    const uint64_t fend = (c_hi * chk < nfloats_file ? c_hi * chk : nfloats_file), nchunks = c_hi - c_lo;
+    for (uint64_t c0 = 0; c0 < nchunks; c0 += ctx->max_chunks) {
+        const uint64_t bbase = (c_lo + c0) * chk; /* file word of the batch's first word */
+        const uint32_t nb = (uint32_t)((nchunks - c0) < ctx->max_chunks ? (nchunks - c0) : ctx->max_chunks);
+        const uint64_t bfl = (fend - bbase) < (uint64_t)nb * chk ? (fend - bbase) : (uint64_t)nb * chk;
+        if (int rc = decode_batch(ctx, rec, len, bfl, nb, chk)) return rc;
+        const int64_t wlo = (int64_t)w0 - (int64_t)bbase;
+        const uint64_t whi = w1 - bbase;
+        const uint64_t span = (whi < bfl ? whi : bfl) - (wlo > 0 ? (uint64_t)wlo : 0u);
+        const uint32_t gx = span / MTILE + 2u < 512u ? (uint32_t)(span / MTILE + 2u) : 512u;
+        LAUNCH("k_merge_window", k_merge_segments<true>, dim3(gx, nb), dim3(256), rec, ctx->scratch + 16, ctx->planes, ctx->segs, ctx->nseg, ctx->segidx, bfl,
+               chk, out, len, (uint64_t)4 * ctx->row_chunks * CHK, int_mode ? 1u : 0u, bbase, wlo, whi);
+    }
+    HIPCHK(hipMemcpyAsync(h_res, ctx->result, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream), "copy result");
+    return MRCZ_OK;
+}
+
+extern "C" int mrcz_uncompress_range(mrcz_ctx_t *ctx, const void *d_records, uint64_t len, uint64_t nfloats_file, uint32_t chk,
+                                     uint64_t first_chunk, uint64_t w0, uint64_t w1, void *d_out, int int_mode, uint64_t *consumed)
+{
+    if (!ctx) return MRCZ_EINVAL;
+    if (consumed) *consumed = 0;
+    if (int rc = uncompress_range_enqueue(ctx, d_records, len, nfloats_file, chk, first_chunk, w0, w1, d_out, ctx->h_result, int_mode)) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream), "stream sync (uncompress range)");
+    if (consumed) *consumed = ctx->h_result[0];
+    ctx->last_fallbacks = ctx->h_result[2];
+    if (ctx->h_result[1]) return fail(ctx, MRCZ_EFORMAT, "malformed chunk records or deflate stream", hipSuccess);
+    return MRCZ_OK;
+}
+
+extern "C" int mrcz_uncompress_range_async(mrcz_ctx_t *ctx, const void *d_records, uint64_t len, uint64_t nfloats_file, uint32_t chk,
+                                           uint64_t first_chunk, uint64_t w0, uint64_t w1, void *d_out, int int_mode, uint64_t *h_result3)
+{
+    return uncompress_range_enqueue(ctx, d_records, len, nfloats_file, chk, first_chunk, w0, w1, d_out, h_result3, int_mode);
 }
 
 /* ---- events and the three streams of a context (pipelines: include/mrcz_hip.h) ---- */

@@ -2624,16 +2624,32 @@ __device__ __forceinline__ uint4 blend16(uint4 a, uint4 b, uint32_t nlow)
     return make_uint4(o[0], o[1], o[2], o[3]);
 }
 
+/* WINDOW (range decode): only the words [wlo, whi) of the batch (batch-relative word indices, wlo may be negative: the window
+ * began in an earlier batch) are produced, word x going to out[x - wlo]; tiles outside the window are not touched.  The
+ * transposed words of a tile are staged in LDS so that every output group of four words that lies inside the tile is written
+ * with one 16-byte store whatever the window's alignment; only the group that straddles a tile edge (or an end of the window)
+ * is stored word by word, by each of the two tiles for its own words. */
+template <bool WINDOW>
 __global__ __launch_bounds__(256) void k_merge_segments(const uint8_t *__restrict__ rec, const uint8_t *__restrict__ scratch,
                                                         const uint8_t *__restrict__ planes, const Seg *__restrict__ segs,
                                                         const uint32_t *__restrict__ nseg, const uint16_t *__restrict__ segidx,
                                                         uint64_t nfloats, uint32_t chk, uint32_t *__restrict__ out, uint64_t reclen,
-                                                        uint64_t planes_bytes, uint32_t int_mode, uint64_t first_float)
+                                                        uint64_t planes_bytes, uint32_t int_mode, uint64_t first_float,
+                                                        int64_t wlo, uint64_t whi)
 {
     __shared__ __attribute__((aligned(16))) uint4 tile[4][MTILE / 16];
     const uint32_t c = blockIdx.y;
     const uint64_t cbase = (uint64_t)c * chk;
     const uint32_t n = (uint32_t)((nfloats - cbase) < chk ? (nfloats - cbase) : chk);
+    /* tiles of this chunk that are merged: all of them, or (WINDOW) [tfirst, tend), those that overlap the window */
+    uint32_t tfirst = 0, tend = 0, wa = 0, wb = n; /* (WINDOW) covering tiles, chunk-relative part of the window */
+    if (WINDOW) {
+        const int64_t a = wlo - (int64_t)cbase, b = (int64_t)whi - (int64_t)cbase;
+        wa = a <= 0 ? 0u : (a >= (int64_t)n ? n : (uint32_t)a);
+        wb = b <= 0 ? 0u : (b >= (int64_t)n ? n : (uint32_t)b);
+        tfirst = wa / (uint32_t)MTILE;
+        tend = wb > wa ? (wb + (uint32_t)MTILE - 1u) / (uint32_t)MTILE : 0u;
+    }
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t s = 4u * c + (uint32_t)__builtin_amdgcn_readfirstlane(w);
     const Seg *sg = segs + (size_t)s * MAXSEG;
@@ -2651,12 +2667,12 @@ __global__ __launch_bounds__(256) void k_merge_segments(const uint8_t *__restric
     Seg Sn[NSEGF];
 #pragma unroll
     for (int i = 0; i < NSEGF; i++) Sn[i] = ZS;
-    if ((uint64_t)blockIdx.x * MTILE < n) {
-        k0n = ns ? (uint32_t)__builtin_amdgcn_readfirstlane((int)segidx[(size_t)s * MTILES + blockIdx.x]) : 0u;
+    if (WINDOW ? tfirst + blockIdx.x < tend : (uint64_t)blockIdx.x * MTILE < n) {
+        k0n = ns ? (uint32_t)__builtin_amdgcn_readfirstlane((int)segidx[(size_t)s * MTILES + tfirst + blockIdx.x]) : 0u;
 #pragma unroll
         for (int i = 0; i < NSEGF; i++) if (k0n + (uint32_t)i < ns) Sn[i] = sg[k0n + (uint32_t)i];
     }
-    for (uint32_t t = blockIdx.x; (uint64_t)t * MTILE < n; t += gridDim.x) {
+    for (uint32_t t = tfirst + blockIdx.x; WINDOW ? t < tend : (uint64_t)t * MTILE < n; t += gridDim.x) {
         const uint32_t p0 = t * MTILE, pend = (n - p0) < (uint32_t)MTILE ? n : p0 + MTILE;
         const uint32_t k0 = k0n;
         Seg S[NSEGF];
@@ -2665,7 +2681,7 @@ __global__ __launch_bounds__(256) void k_merge_segments(const uint8_t *__restric
 #pragma unroll
         for (int i = 0; i < NSEGF; i++) { S[i] = Sn[i]; base[i] = seg_base(sb, S[i].src); send[i] = S[i].dst + S[i].len; }
         const uint32_t tn = t + gridDim.x;
-        const bool more = (uint64_t)tn * MTILE < n;
+        const bool more = WINDOW ? tn < tend : (uint64_t)tn * MTILE < n;
         if (more) k0n = ns ? (uint32_t)__builtin_amdgcn_readfirstlane((int)segidx[(size_t)s * MTILES + tn]) : 0u;
         /* A group of 16 bytes that straddles a boundary X | Y of two consecutive segments (one per boundary) is read twice --
          * once relative to each segment, reading a few bytes past X's end and before Y's start -- and blended: no byte loop, no
@@ -2724,10 +2740,11 @@ __global__ __launch_bounds__(256) void k_merge_segments(const uint8_t *__restric
             tile[w][g] = v[j];
         }
         __syncthreads();
+        uint4 wv[MTILE / 4 / 256]; /* (WINDOW) this thread's transposed words, staged in LDS once every wave has read the planes */
 #pragma unroll
         for (int j = 0; j < MTILE / 4 / 256; j++) {
             const uint32_t q = threadIdx.x + 256u * (uint32_t)j, i = p0 + 4u * q;
-            if (i >= n) continue;
+            if (!WINDOW && i >= n) continue;
             const uint32_t a = reinterpret_cast<const uint32_t *>(tile[0])[q], b = reinterpret_cast<const uint32_t *>(tile[1])[q];
             const uint32_t cc = reinterpret_cast<const uint32_t *>(tile[2])[q], dd = reinterpret_cast<const uint32_t *>(tile[3])[q];
             /* 4x4 byte transpose back */
@@ -2745,6 +2762,7 @@ __global__ __launch_bounds__(256) void k_merge_segments(const uint8_t *__restric
                 if (fi + 2u >= 256u) o4.z = dequant_int8(o4.z);
                 if (fi + 3u >= 256u) o4.w = dequant_int8(o4.w);
             }
+            if (WINDOW) { wv[j] = o4; continue; }
             uint32_t *o = out + cbase + i;
             if (i + 4u <= n && (((uintptr_t)o) & 15u) == 0) *reinterpret_cast<uint4 *>(o) = o4;
             else {
@@ -2752,6 +2770,30 @@ __global__ __launch_bounds__(256) void k_merge_segments(const uint8_t *__restric
                 if (i + 1u < n) o[1] = o4.y;
                 if (i + 2u < n) o[2] = o4.z;
                 if (i + 3u < n) o[3] = o4.w;
+            }
+        }
+        if (WINDOW) {
+            __syncthreads(); /* every wave has read its planes out of `tile`: it now holds the tile's words */
+            uint4 *tw = &tile[0][0];
+#pragma unroll
+            for (int j = 0; j < MTILE / 4 / 256; j++) tw[threadIdx.x + 256u * (uint32_t)j] = wv[j];
+            __syncthreads();
+            const uint32_t *tws = reinterpret_cast<const uint32_t *>(tw);
+            /* the tile's part of the window, chunk-relative words [ta, tb); output index of chunk word i: i + obias */
+            const uint32_t ta = p0 > wa ? p0 : wa, tb = pend < wb ? pend : wb;
+            const int64_t obias = (int64_t)cbase - wlo;
+            const int64_t oa = (int64_t)ta + obias, ob = (int64_t)tb + obias; /* output words [oa, ob), oa >= 0 */
+            const int64_t g0 = oa >> 2, g1 = (ob + 3) >> 2;                  /* output groups of four words touched */
+            for (int64_t g = g0 + threadIdx.x; g < g1; g += 256) {
+                const int64_t o0 = 4 * g;
+                const int64_t i0 = o0 - obias - (int64_t)p0; /* tile-relative word of output word o0 (may be < 0 or past the tile) */
+                uint32_t *o = out + o0;
+                if (o0 >= oa && o0 + 4 <= ob) { /* all four words inside this tile and the window: one 16-byte store */
+                    *reinterpret_cast<uint4 *>(o) = make_uint4(tws[i0], tws[i0 + 1], tws[i0 + 2], tws[i0 + 3]);
+                } else {
+                    for (int k = 0; k < 4; k++)
+                        if (o0 + k >= oa && o0 + k < ob) o[k] = tws[i0 + k];
+                }
             }
         }
         __syncthreads();

@@ -1,0 +1,177 @@
+/*
+ * mrc_extract.c -- range decode from the command line: part of a container without reading or decoding the rest.
+ *
+ *   mrc_extract -i vol.mrc.zip -o out.raw (-w first:count | -z z0:z1) [-s float|int] [-g device]
+ *
+ *   -w first:count   words [first, first + count) of the decoded file (4 bytes each)
+ *   -z z0:z1         sections [z0, z1) of a float32 (mode 2) MRC volume: nx, ny, nz, mode (bytes 0-15) and nsymbt (bytes 92-95)
+ *                    come from the decoded first 256 words, the data start at byte 1024 + nsymbt
+ *   -s               decode mode, as mrc_tar -s (the container does not record it)
+ *
+ * The 17-byte file header and the 16-byte header of every chunk before the window are read with pread; then only the records of
+ * the chunks that cover the window, which mrcz_uncompress_range decodes (in one call: the covering records and the window must
+ * fit in device memory; the workspace is batched as in every decode).  Not one of the reference's front ends: mrc_tar and
+ * mrc_tarx keep the reference's command lines.
+ */
+#include "../../include/mrcz_hip.h"
+
+#include <errno.h>
+#include <fcntl.h>
+#include <inttypes.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <unistd.h>
+
+#define MRC_HEADER_BYTES 1024u
+
+static void usage(const char *prog)
+{
+    printf("\nUsage:\n\n\t%s -i <container> -o <output file> (-w <first>:<count> | -z <z0>:<z1>) [-s float|int] [-g device]\nwhere:\n", prog);
+    printf("\t-i\tcontainer written by mrc_tar -t zip\n\n");
+    printf("\t-o\traw output: the decoded words of the window, 4 bytes each\n\n");
+    printf("\t-w\twords [first, first + count) of the decoded file\n\n");
+    printf("\t-z\tsections [z0, z1) of a float32 (mode 2) MRC volume\n\n");
+    printf("\t-s\tdata type the container was written with, [float | int], default float\n\n");
+    printf("\t-g\tHIP device, default 0\n\n");
+}
+
+/* errors leave with the reference's exit(-1) status (255), never through a signal; stdio is flushed by hand and no exit handlers
+ * run (the HIP runtime's destructors are not needed to release anything a dying process holds) */
+static void die(const char *what, mrcz_ctx_t *c)
+{
+    fprintf(stderr, "[%s:%d] ERROR: %s%s%s\n", __FILE__, __LINE__, what, c ? ": " : "", c ? mrcz_last_error(c) : "");
+    fflush(stdout);
+    fflush(stderr);
+    _exit(255);
+}
+
+static int parse_pair(const char *s, uint64_t *a, uint64_t *b)
+{
+    char *e = NULL;
+    errno = 0;
+    if (*s < '0' || *s > '9') return -1;
+    *a = strtoull(s, &e, 10);
+    if (errno || *e != ':' || e[1] < '0' || e[1] > '9') return -1;
+    *b = strtoull(e + 1, &e, 10);
+    return (errno || *e) ? -1 : 0;
+}
+
+static void pread_all(int fd, void *buf, uint64_t n, uint64_t off, const char *what)
+{
+    uint8_t *p = (uint8_t *)buf;
+    while (n) {
+        const ssize_t r = pread(fd, p, n > (1u << 30) ? (1u << 30) : (size_t)n, (off_t)off);
+        if (r <= 0) die(what, NULL);
+        p += r; n -= (uint64_t)r; off += (uint64_t)r;
+    }
+}
+
+struct container {
+    int fd;
+    uint64_t nfl; /* words of the decoded file */
+    uint32_t chk;
+    signed char ztypes[4];
+};
+
+/* words [w0, w1) of the file, decoded on the device, into a malloc'ed host buffer */
+static uint32_t *decode_window(mrcz_ctx_t **pc, int device, const struct container *ct, uint64_t w0, uint64_t w1, int int_mode)
+{
+    const uint64_t chk = ct->chk, c_lo = w0 / chk, c_hi = (w1 + chk - 1) / chk;
+    uint64_t off = MRCZ_FILE_HEADER_BYTES, start = 0;
+    for (uint64_t c = 0; c < c_hi; c++) { /* 16 bytes per chunk up to the window's last one */
+        uint8_t h[16];
+        uint64_t bytes = 0;
+        const uint64_t left = ct->nfl - c * chk;
+        if (c == c_lo) start = off;
+        pread_all(ct->fd, h, 16, off, "truncated container (chunk header)");
+        if (mrcz_record_size(h, (uint32_t)(left < chk ? left : chk), &bytes) != MRCZ_OK) die("damaged chunk header", NULL);
+        off += bytes;
+    }
+    const uint64_t len = off - start, n = w1 - w0;
+    if (!*pc) {
+        const uint64_t nch = c_hi - c_lo;
+        if (mrcz_create(pc, device, (uint32_t)(nch < 16 ? nch : 16)) != MRCZ_OK) die("no usable HIP device (the codec has no CPU path)", NULL);
+    }
+    mrcz_ctx_t *c = *pc;
+    if (mrcz_set_ztypes(c, ct->ztypes) != MRCZ_OK) die("byte stream compressor types", c);
+    void *h_rec = NULL, *d_rec = NULL, *d_out = NULL;
+    uint32_t *out = (uint32_t *)malloc(4 * n);
+    if (!out || mrcz_host_malloc(c, &h_rec, len) || mrcz_dev_malloc(c, &d_rec, len) || mrcz_dev_malloc(c, &d_out, 4 * n)) die("out of memory", c);
+    pread_all(ct->fd, h_rec, len, start, "truncated container (payload)");
+    uint64_t consumed = 0;
+    if (mrcz_copy_h2d(c, d_rec, h_rec, len) != MRCZ_OK) die("copy to the device", c);
+    if (mrcz_uncompress_range(c, d_rec, len, ct->nfl, ct->chk, c_lo, w0, w1, d_out, int_mode, &consumed) != MRCZ_OK) die("range decode", c);
+    if (mrcz_copy_d2h(c, out, d_out, 4 * n) != MRCZ_OK) die("copy from the device", c);
+    mrcz_dev_free(c, d_out);
+    mrcz_dev_free(c, d_rec);
+    mrcz_host_free(c, h_rec);
+    return out;
+}
+
+int main(int argc, char *argv[])
+{
+    const char *in = NULL, *outp = NULL, *wspec = NULL, *zspec = NULL, *dtype = "float";
+    int opt, device = 0;
+    if (argc < 2) { usage(argv[0]); return 255; }
+    while ((opt = getopt(argc, argv, "hi:o:w:z:s:g:")) != -1) {
+        switch (opt) {
+        case 'i': in = optarg; break;
+        case 'o': outp = optarg; break;
+        case 'w': wspec = optarg; break;
+        case 'z': zspec = optarg; break;
+        case 's': dtype = optarg; break;
+        case 'g': device = atoi(optarg); break;
+        case 'h': usage(argv[0]); return 0;
+        default: usage(argv[0]); return 255;
+        }
+    }
+    if (!in || !outp || !!wspec == !!zspec) { usage(argv[0]); die("need -i, -o and one of -w, -z", NULL); }
+    const int int_mode = strcmp(dtype, "int") == 0;
+    if (!int_mode && strcmp(dtype, "float") != 0) die("-s must be float or int", NULL);
+    uint64_t a = 0, b = 0;
+    if (parse_pair(wspec ? wspec : zspec, &a, &b)) die(wspec ? "-w wants first:count" : "-z wants z0:z1", NULL);
+
+    struct container ct;
+    ct.fd = open(in, O_RDONLY);
+    if (ct.fd < 0) die("cannot open the container", NULL);
+    uint8_t fh[MRCZ_FILE_HEADER_BYTES]; /* write_mrczip_header: u64 fsz, u32 chk, i8 type, i8 ztypes[4] */
+    pread_all(ct.fd, fh, sizeof fh, 0, "container shorter than its 17-byte header");
+    uint64_t fsz = 0;
+    memcpy(&fsz, fh, 8);
+    memcpy(&ct.chk, fh + 8, 4);
+    memcpy(ct.ztypes, fh + 13, 4);
+    ct.nfl = fsz / 4;
+    if (ct.chk == 0 || ct.chk > MRCZ_CHUNK_FLOATS) die("chunk size in the file header out of range", NULL);
+    for (int j = 0; j < 4; j++)
+        if (ct.ztypes[j] != 0 && ct.ztypes[j] != 2 && ct.ztypes[j] != 4) die("unknown byte stream compressor type in the file header", NULL);
+
+    mrcz_ctx_t *c = NULL;
+    uint64_t w0, w1;
+    if (wspec) {
+        w0 = a;
+        w1 = a + b;
+        if (b == 0 || w1 < w0 || w1 > ct.nfl) die("-w window empty or past the end of the file", NULL);
+    } else {
+        if (ct.nfl < MRC_HEADER_BYTES / 4) die("file shorter than an MRC header", NULL);
+        uint32_t *hdr = decode_window(&c, device, &ct, 0, MRC_HEADER_BYTES / 4, 0);
+        int32_t nx = (int32_t)hdr[0], ny = (int32_t)hdr[1], nz = (int32_t)hdr[2], mode = (int32_t)hdr[3], nsymbt = (int32_t)hdr[23];
+        free(hdr);
+        if (mode != 2) die("only float32 (mode 2) MRC volumes can be cut into sections", NULL);
+        if (nx <= 0 || ny <= 0 || nz <= 0 || nsymbt < 0 || (nsymbt & 3)) die("implausible MRC header (nx, ny, nz, nsymbt)", NULL);
+        if (a >= b || b > (uint64_t)nz) die("-z sections outside the volume", NULL);
+        const uint64_t sec = (uint64_t)nx * (uint64_t)ny;
+        w0 = (MRC_HEADER_BYTES + (uint64_t)nsymbt) / 4 + a * sec;
+        w1 = w0 + (b - a) * sec;
+        if (w1 > ct.nfl) die("the MRC header describes more data than the file holds", NULL);
+    }
+    uint32_t *out = decode_window(&c, device, &ct, w0, w1, int_mode);
+    FILE *fo = fopen(outp, "wb");
+    if (!fo) die("cannot open the output file", NULL);
+    if (fwrite(out, 4, (size_t)(w1 - w0), fo) != (size_t)(w1 - w0) || fclose(fo) != 0) die("write", NULL);
+    printf("words [%" PRIu64 ", %" PRIu64 ") of %" PRIu64 " written to %s\n", w0, w1, ct.nfl, outp);
+    free(out);
+    close(ct.fd);
+    fflush(stdout);
+    _exit(0); /* (as mrc_tar: the process's death releases the device memory; skipping the runtime's teardown saves 0.1 s) */
+}

@@ -149,6 +149,31 @@ int mrcz_compress_chunks_int8_async(mrcz_ctx_t *ctx, const void *d_in, uint64_t 
 int mrcz_uncompress_chunks_int8_async(mrcz_ctx_t *ctx, const void *d_records, uint64_t len, uint64_t nfloats, uint32_t chk,
                                       uint64_t first_chunk, void *d_out, uint64_t *h_result3);
 
+/*
+ * Range decode: words [w0, w1) of a file without decoding the rest.  Nothing in the container changes: every chunk record
+ * starts with a 16-byte header holding its four payload lengths, so where chunk c's record begins follows from the headers
+ * of chunks 0 .. c-1 alone, and the chunks decode independently.  Only the chunks that cover the window are decoded (whole),
+ * and only the window's words are merged back into floats.
+ *   mrcz_record_size      bytes of one chunk record (header included) from its 16-byte header, for a chunk of n floats;
+ *                         MRCZ_EFORMAT for lengths no record of such a chunk can have
+ *   mrcz_records_index    (host memory) byte offset, from the first record, of every chunk record of a file of nfloats floats
+ *                         in chunks of chk: offsets[0 .. nchunks], offsets[nchunks] = end of the last record.  Reads 16 bytes
+ *                         per chunk; MRCZ_EFORMAT if the records end early
+ *   mrcz_uncompress_range d_records/len = the records of chunks first_chunk, first_chunk + 1, ... of a file of nfloats_file
+ *                         floats (first_chunk <= w0 / chk; records before the window's first chunk are only walked);
+ *                         d_out (16-byte aligned) receives the w1 - w0 words; int_mode = the "-s int" decode
+ *                         (mrcz_uncompress_chunks_int8).  mrcz_set_ztypes applies.  w0 >= w1, w1 > nfloats_file or
+ *                         first_chunk past the window: MRCZ_EINVAL; records that end before the window's last chunk:
+ *                         MRCZ_EFORMAT (never read past len).  consumed = bytes of d_records up to the end of the last
+ *                         record decoded.
+ */
+int mrcz_record_size(const void *h_header16, uint32_t n, uint64_t *bytes);
+int mrcz_records_index(const void *h_records, uint64_t len, uint64_t nfloats, uint32_t chk, uint64_t *offsets);
+int mrcz_uncompress_range(mrcz_ctx_t *ctx, const void *d_records, uint64_t len, uint64_t nfloats_file, uint32_t chk,
+                          uint64_t first_chunk, uint64_t w0, uint64_t w1, void *d_out, int int_mode, uint64_t *consumed);
+int mrcz_uncompress_range_async(mrcz_ctx_t *ctx, const void *d_records, uint64_t len, uint64_t nfloats_file, uint32_t chk,
+                                uint64_t first_chunk, uint64_t w0, uint64_t w1, void *d_out, int int_mode, uint64_t *h_result3);
+
 /* apply_mask alone on device (the erasebytes restatement used by the GPU-side verification tools,
  * src/tool/erasebytes.c:109-134): words [256, nwords) of a file &= mask(bits).  In place. */
 int mrcz_erase_bits(mrcz_ctx_t *ctx, void *d_words, uint64_t nwords, uint64_t first_word_index, int bits);
