@@ -23,7 +23,21 @@
 using namespace mrcz;
 
 #define MAX_TIMERS 32
-#define MAX_LANES 4
+
+/* Lanes per compress batch (see compress_enqueue): 2 measured best (1: 292, 2: 306, 3: 307, 4: 229 GB/s -- with four Huffman
+ * kernels resident their 72 KB workgroups starve the streaming kernels of LDS) */
+constexpr int MAX_LANES = 2;
+/* two lanes: share of a batch's chunks (per cent) the first lane takes (measured: 50 -> 2.58 ms, 55 -> 2.56, 60 -> 2.60; three
+ * lanes, even or uneven, 2.8-2.9) */
+constexpr uint32_t SPLIT_PCT = 55;
+/* k_histogram: lanes that must share lane 0's first byte for a tile to count per value in the wave (1 GiB, k_histogram in us at
+ * 4 / 8 / 12 / 16: detector counts 559 / 488 / 597 / 642, Gaussian 490 / 372 / 368 / 375, 64 values per plane 808 / 376 / 358 / 359) */
+constexpr uint32_t HIST_FEW = 8;
+/* the block decoder runs as a fixed grid of three workgroups per CU (its LDS footprint admits exactly three) */
+constexpr uint32_t BLK_WGS_PER_CU = 3;
+/* k_validate_wave's grid: ~280 signature survivors per stream; the more waves in flight, the better their memory round trips
+ * overlap (1 GiB: 2048 waves 279 us, 8192 159, 32768 128) */
+static uint32_t validate_grid(uint32_t ns) { return ns * 192u < 4096u ? 4096u : ns * 192u > 32768u ? 32768u : ns * 192u; }
 
 struct mrcz_ctx {
     int device;
@@ -34,19 +48,7 @@ struct mrcz_ctx {
     hipStream_t lane_stream[MAX_LANES]; /* ... the lanes of a compress batch (see mrcz_compress_chunks); [0] = stream */
     hipEvent_t ev_start, ev_cont, ev_done[MAX_LANES];
     hipEvent_t ev_stream[MAX_LANES]; /* lane l's summary + histogram passes are done */
-    uint32_t huff_split;           /* the blocks' dynamic headers by k_huffman_hdr, one wave per tree (MRCZ_HUFF_SPLIT=0: inside k_huffman, one thread per tree) */
-    uint32_t validate_wave, validate_grid; /* candidate headers: one wave each (MRCZ_VALIDATE_WAVE=0: one lane each) */
-    uint32_t use_hint;             /* block decoder: size the pieces of a window by where the block probably ends (MRCZ_HINT=0: off) */
-    uint32_t split_pct;            /* two lanes: share of a batch's chunks (per cent) the first lane takes; MRCZ_SPLIT overrides it */
-    int stagger;                   /* lanes start one after the other (each once the previous one's streaming passes are done), so that
-                                    * their Huffman kernels -- one tree's latency long, nearly idle machine -- run under the other lanes'
-                                    * bandwidth-bound passes instead of side by side */
-    int huff_ht;                   /* trees per Huffman workgroup (16 / 32 / 48) */
-    uint32_t lanes;                /* lanes per compress batch: 2 measured best (1: 292, 2: 306, 3: 307, 4: 229 GB/s -- with four
-                                    * Huffman kernels resident their 72 KB workgroups starve the streaming kernels of LDS);
-                                    * MRCZ_LANES overrides it for experiments */
-    uint32_t hist_few;             /* k_histogram: lanes that must share lane 0's first byte for a tile to count per value in the wave (MRCZ_HIST_FEW) */
-    uint32_t hist_waves;           /* waves per k_histogram workgroup: 0 = by batch size (4 up to 12 chunks, else 1); MRCZ_HIST_WAVES=1|4 forces */
+    uint32_t lanes;                /* lanes per compress batch: MAX_LANES, or 1 for batches under 8 chunks */
     int trace;                     /* MRCZ_TRACE: the synchronous calls print how long their enqueue and the wait for the device took */
     char err[256];
     /* workspace (sized for max_chunks chunks = 4*max_chunks streams) */
@@ -146,15 +148,12 @@ extern "C" int mrcz_create(mrcz_ctx_t **out, int device, uint32_t max_batch_chun
     hipError_t e = hipSuccess;
     if (e == hipSuccess) e = hipStreamCreate(&ctx->stream);
     ctx->lane_stream[0] = ctx->stream;
-    ctx->lanes = 2;
-    if (const char *ev = getenv("MRCZ_LANES")) { const int v = atoi(ev); if (v >= 1 && v <= MAX_LANES) ctx->lanes = (uint32_t)v; }
-    if (max_batch_chunks < 8u) ctx->lanes = 1; /* batches under 8 chunks run as one lane anyway */
+    ctx->lanes = max_batch_chunks < 8u ? 1u : (uint32_t)MAX_LANES; /* batches under 8 chunks run as one lane anyway */
     for (uint32_t l = 1; l < ctx->lanes && e == hipSuccess; l++) e = hipStreamCreate(&ctx->lane_stream[l]); /* (stream priorities were tried: no effect on the lanes' overlap) */
-    {   /* the block decoder runs as a fixed grid of three workgroups per CU (its LDS footprint admits exactly three) */
+    {
         hipDeviceProp_t prop;
-        ctx->blk_grid = 768;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ctx->blk_grid = 3u * (uint32_t)prop.multiProcessorCount;
-        if (const char *ev = getenv("MRCZ_BLK_GRID")) { const int v = atoi(ev); if (v >= 1 && v <= 65535) ctx->blk_grid = (uint32_t)v; }
+        ctx->blk_grid = BLK_WGS_PER_CU * 256u;
+        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ctx->blk_grid = BLK_WGS_PER_CU * (uint32_t)prop.multiProcessorCount;
     }
     /* workspace rows (one per stream): every compress lane owns a fixed range of ceil(max_chunks / lanes) chunk rows */
     ctx->row_chunks = ctx->lanes * ((max_batch_chunks + ctx->lanes - 1u) / ctx->lanes);
@@ -166,23 +165,6 @@ extern "C" int mrcz_create(mrcz_ctx_t **out, int device, uint32_t max_batch_chun
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_cont, hipEventDisableTiming);
     for (int l = 0; l < MAX_LANES && e == hipSuccess; l++) e = hipEventCreateWithFlags(&ctx->ev_done[l], hipEventDisableTiming);
     for (int l = 0; l < MAX_LANES && e == hipSuccess; l++) e = hipEventCreateWithFlags(&ctx->ev_stream[l], hipEventDisableTiming);
-    ctx->stagger = 1;
-    ctx->huff_ht = 48;
-    ctx->split_pct = 55; /* (measured: 50 -> 2.58 ms, 55 -> 2.56, 60 -> 2.60; three lanes, even or uneven, 2.8-2.9) */
-    ctx->use_hint = 1;
-    ctx->huff_split = 1;
-    ctx->validate_wave = 1;
-    ctx->hist_few = 8; /* (1 GiB, k_histogram in us at 4 / 8 / 12 / 16: detector counts 559 / 488 / 597 / 642, Gaussian 490 / 372 / 368 / 375, 64 values per plane 808 / 376 / 358 / 359) */
-    if (const char *ev = getenv("MRCZ_HIST_FEW")) { const int v = atoi(ev); if (v >= 1 && v <= 65) ctx->hist_few = (uint32_t)v; }
-    if (const char *ev = getenv("MRCZ_HIST_WAVES")) { const int v = atoi(ev); if (v == 1 || v == 4) ctx->hist_waves = (uint32_t)v; }
-    ctx->validate_grid = 0; /* 0 = by the batch's stream count */
-    if (const char *ev = getenv("MRCZ_VALIDATE_WAVE")) ctx->validate_wave = atoi(ev) ? 1u : 0u;
-    if (const char *ev = getenv("MRCZ_VALIDATE_GRID")) { const int v = atoi(ev); if (v >= 1 && v <= 65535) ctx->validate_grid = (uint32_t)v; }
-    if (const char *ev = getenv("MRCZ_HUFF_SPLIT")) ctx->huff_split = atoi(ev) ? 1u : 0u;
-    if (const char *ev = getenv("MRCZ_HINT")) ctx->use_hint = atoi(ev) ? 1u : 0u;
-    if (const char *ev = getenv("MRCZ_SPLIT")) { const int v = atoi(ev); if (v >= 5 && v <= 95) ctx->split_pct = (uint32_t)v; }
-    if (const char *ev = getenv("MRCZ_STAGGER")) ctx->stagger = atoi(ev) ? 1 : 0;
-    if (const char *ev = getenv("MRCZ_HT")) { const int v = atoi(ev); if (v == 16 || v == 32 || v == 48) ctx->huff_ht = v; }
     t_streams = wall_now();
     if (e == hipSuccess) e = dalloc(&ctx->tsum, ns * TPS);
     if (e == hipSuccess) e = dalloc(&ctx->tinfo, ns * TPS);
@@ -362,21 +344,17 @@ static int compress_lane(mrcz_ctx *ctx, hipStream_t lstream, int phase, int slot
         if (int_mode) LAUNCH("k_tile_summary", k_tile_summary<true>, dim3(SPS, nb), dim3(256), bin, bfl, mask, fstart, tsum, planes);
         else LAUNCH("k_tile_summary", k_tile_summary<false>, dim3(SPS, nb), dim3(256), bin, bfl, mask, fstart, tsum, planes);
         LAUNCH("k_stream_scan", k_stream_scan, dim3(ns), dim3(256), tsum, bfl, tinfo, sinfo, blkstart);
-        if (ctx->hist_waves ? ctx->hist_waves == 4u : nb <= 12u) LAUNCH("k_histogram", k_histogram<4>, dim3(SPS, nb, 4), dim3(256), planes, bfl, tinfo, pairhist, blkstart, slideq, ctx->hist_few);
-        else LAUNCH("k_histogram", k_histogram<1>, dim3(SPS, nb, 4), dim3(64), planes, bfl, tinfo, pairhist, blkstart, slideq, ctx->hist_few);
+        /* waves per workgroup by batch size: 4 up to 12 chunks, else 1 */
+        if (nb <= 12u) LAUNCH("k_histogram", k_histogram<4>, dim3(SPS, nb, 4), dim3(256), planes, bfl, tinfo, pairhist, blkstart, slideq, HIST_FEW);
+        else LAUNCH("k_histogram", k_histogram<1>, dim3(SPS, nb, 4), dim3(64), planes, bfl, tinfo, pairhist, blkstart, slideq, HIST_FEW);
         LAUNCH("k_block_reduce", k_block_reduce, dim3(MAXBLK, ns), dim3(64), tinfo, sinfo, pairhist, blkfreq);
         LAUNCH("k_block_index", k_block_index, dim3(1), dim3(256), sinfo, ns, blkbase);
         HIPCHK(hipEventRecord(ctx->ev_stream[slot], lstream), "event"); /* this lane's streaming passes are done: the next lane may start */
         unsigned long long *hdbg = ctx->phase_profile == 3 ? ctx->dbgphase : (unsigned long long *)NULL; /* developer tool */
-        if (ctx->huff_split) {
-            /* trees one thread each, then the header of every block one wave each (the grid covers the most blocks a batch can
-             * have; the kernel reads the count from blkbase) */
-            LAUNCH("k_huffman", (k_huffman<48, false>), dim3((ns * MAXBLK + 47) / 48), dim3(48), sinfo, ns, blkbase, blkfreq, blkcode, blkhdr, meta, hdbg);
-            LAUNCH("k_huffman_hdr", k_huffman_hdr, dim3(ns * MAXBLK), dim3(64), sinfo, ns, blkbase, blkcode, blkhdr, meta);
-        } else if (ctx->huff_ht == 16) LAUNCH("k_huffman", (k_huffman<16, true>), dim3((ns * MAXBLK + 15) / 16), dim3(16), sinfo, ns, blkbase, blkfreq, blkcode, blkhdr, meta, hdbg);
-        else if (ctx->huff_ht == 32) LAUNCH("k_huffman", (k_huffman<32, true>), dim3((ns * MAXBLK + 31) / 32), dim3(32), sinfo, ns, blkbase, blkfreq, blkcode, blkhdr, meta, hdbg);
-        else LAUNCH("k_huffman", (k_huffman<48, true>), dim3((ns * MAXBLK + 47) / 48), dim3(48), sinfo, ns, blkbase, blkfreq, blkcode, blkhdr, meta, hdbg);
-
+        /* trees one thread each, then the header of every block one wave each (the grid covers the most blocks a batch can
+         * have; the kernel reads the count from blkbase) */
+        LAUNCH("k_huffman", k_huffman, dim3((ns * MAXBLK + HUFF_TREES - 1) / HUFF_TREES), dim3(HUFF_TREES), sinfo, ns, blkbase, blkfreq, blkcode, blkhdr, meta, hdbg);
+        LAUNCH("k_huffman_hdr", k_huffman_hdr, dim3(ns * MAXBLK), dim3(64), sinfo, ns, blkbase, blkcode, blkhdr, meta);
         LAUNCH("k_stream_layout", k_stream_layout, dim3(ns), dim3(64), sinfo, meta, blkstart, slideq, lay);
         LAUNCH("k_pair_bits", k_pair_bits, dim3(SPS, ns), dim3(64), sinfo, lay, pairhist, blkcode, tinfo, pairbits);
         LAUNCH("k_pair_offsets", k_pair_offsets, dim3(ns), dim3(64), sinfo, lay, tinfo, pairbits, pairoff);
@@ -428,16 +406,16 @@ static int compress_enqueue(mrcz_ctx_t *ctx, const void *d_in, uint64_t nfloats,
     for (uint64_t c0 = 0; c0 < nchunks; c0 += ctx->max_chunks) {
         const uint32_t nb = (uint32_t)((nchunks - c0) < ctx->max_chunks ? (nchunks - c0) : ctx->max_chunks);
         /* small batches are launch-bound: a second lane doubles the launches (64 MiB: 78 -> 69 GB/s with two lanes) */
-        const uint32_t nlanes = (ctx->timing || nb < 8u) ? 1u : (nb < ctx->lanes ? nb : ctx->lanes);
+        const uint32_t nlanes = (ctx->timing || nb < 8u) ? 1u : ctx->lanes;
         const uint64_t bfl = (nfloats - c0 * CHK) < (uint64_t)nb * CHK ? (nfloats - c0 * CHK) : (uint64_t)nb * CHK;
         ctx->last_streams = 4u * nb;
         ctx->last_nlanes = nlanes;
-        uint32_t lc0[MAX_LANES + 1]; /* first chunk (inside the batch) of every lane */
-        for (uint32_t l = 0; l <= nlanes; l++) lc0[l] = (uint32_t)(((uint64_t)nb * l) / nlanes);
+        uint32_t lc0[MAX_LANES + 1] = {0u, nb}; /* first chunk (inside the batch) of every lane, then the batch's end */
         if (nlanes == 2u) {
-            lc0[1] = (uint32_t)(((uint64_t)nb * ctx->split_pct + 50u) / 100u);
+            lc0[1] = (uint32_t)(((uint64_t)nb * SPLIT_PCT + 50u) / 100u);
             if (lc0[1] < 1u) lc0[1] = 1u;
             if (lc0[1] > nb - 1u) lc0[1] = nb - 1u;
+            lc0[2] = nb;
         }
         bool same_rows = prev_lanes == nlanes;
         for (uint32_t l = 0; same_rows && l < nlanes; l++) same_rows = prev_lc0[l] == lc0[l];
@@ -466,9 +444,10 @@ static int compress_enqueue(mrcz_ctx_t *ctx, const void *d_in, uint64_t nfloats,
                      * that lane's streaming passes are through and its Huffman kernel is next in line. */
                     HIPCHK(hipStreamWaitEvent(st, ctx->ev_stream[l + 1u], 0), "wait");
                 }
-                if (phase == 0 && ctx->stagger && nlanes > 1) {
-                    /* start after the streaming passes of the lane submitted just before this one (the last lane of the
-                     * previous batch for lane 0) */
+                if (phase == 0 && nlanes > 1) {
+                    /* Lanes start one after the other: after the streaming passes of the lane submitted just before this one
+                     * (the last lane of the previous batch for lane 0).  Their Huffman kernels -- one tree's latency long,
+                     * nearly idle machine -- then run under the other lanes' bandwidth-bound passes instead of side by side. */
                     if (stream_pending >= 0 && stream_pending != (int)l) HIPCHK(hipStreamWaitEvent(st, ctx->ev_stream[stream_pending], 0), "wait");
                     stream_pending = (int)l;
                 }
@@ -576,18 +555,13 @@ static int decode_batch(mrcz_ctx_t *ctx, const uint8_t *rec, uint64_t len, uint6
         else
             LAUNCH("k_scan_candidates", k_scan_candidates<SLAB_BYTES>, dim3((CHK + (CHK >> 3) + SLAB_BYTES - 1) / SLAB_BYTES, ns), dim3(64), rec, len,
                    ctx->dstreams, ctx->cands, ctx->ncand, ctx->rawlist, ctx->njobs + 4, ctx->rawcap);
-        if (ctx->validate_wave) /* ~280 signature survivors per stream; the more waves in flight, the better their memory round trips overlap (1 GiB: 2048 waves 279 us, 8192 159, 32768 128) */
-            LAUNCH("k_validate_candidates", k_validate_wave, dim3(ctx->validate_grid ? ctx->validate_grid : (ns * 192u < 4096u ? 4096u : ns * 192u > 32768u ? 32768u : ns * 192u)), dim3(64), rec, len, ctx->dstreams, ctx->rawlist, ctx->njobs + 4,
-                   ctx->rawcap, ctx->cands, ctx->ncand, ctx->hdrs, ctx->calltag);
-        else
-            LAUNCH("k_validate_candidates", k_validate_candidates, dim3(2048), dim3(64), rec, len, ctx->dstreams, ctx->rawlist, ctx->njobs + 4,
-                   ctx->rawcap, ctx->cands, ctx->ncand, ctx->hdrs, ctx->calltag,
-                   ctx->phase_profile == 4 ? ctx->dbgphase + (size_t)ns * 8 : (unsigned long long *)NULL);
+        LAUNCH("k_validate_candidates", k_validate_wave, dim3(validate_grid(ns)), dim3(64), rec, len, ctx->dstreams, ctx->rawlist, ctx->njobs + 4,
+               ctx->rawcap, ctx->cands, ctx->ncand, ctx->hdrs, ctx->calltag);
         LAUNCH("k_cand_index", k_cand_index, dim3(1), dim3(256), ctx->ncand, ctx->dstreams, ns, ctx->candbase, ctx->jobord);
         /* fixed grid: the workgroups pull candidate numbers from ctx->njobs[0] until it passes candbase[ns] (no read-back) */
         LAUNCH("k_blk_count", k_blk_count, dim3(ctx->blk_grid), dim3(PT), rec, len, ctx->dstreams, ns, ctx->candbase, ctx->jobord,
                  ctx->cands, ctx->scratch + 16, ctx->njobs + 2, (uint32_t)(ctx->scratch_bytes >> 4), ctx->hdrs, ctx->calltag, ctx->njobs,
-                 ctx->phase_profile == 2 ? ctx->dbgphase : (unsigned long long *)NULL, ctx->use_hint);
+                 ctx->phase_profile == 2 ? ctx->dbgphase : (unsigned long long *)NULL);
     }
     LAUNCH("k_chain", k_chain, dim3(ns), dim3(64), rec, len, ctx->dstreams, ctx->cands, ctx->ncand, ctx->segs, ctx->nseg, ctx->segidx,
            ctx->fallback, ctx->phase_profile == 1 ? 1u : 0u, ctx->phase_profile == 4 ? ctx->dbgphase : (unsigned long long *)NULL);

@@ -869,9 +869,7 @@ __device__ __forceinline__ void packer_finish(LanePacker &p)
     if (p.nacc > 0) atomicOr(&p.stage[p.word], (uint32_t)p.acc);
 }
 
-#ifndef EMIT_WAVES
-#define EMIT_WAVES 5 /* waves per SIMD: 94 VGPRs, no spills, 6.1 KB of LDS per wave (4: 104 VGPRs, kernel 1.00 ms instead of 0.90; 6: 80 VGPRs, ten of them spilled, 0.93) */
-#endif
+constexpr int EMIT_WAVES = 5; /* waves per SIMD: 94 VGPRs, no spills, 6.1 KB of LDS per wave (4: 104 VGPRs, kernel 1.00 ms instead of 0.90; 6: 80 VGPRs, ten of them spilled, 0.93) */
 #define OPAQUE4(x, q) asm volatile("" : "+v"((x)[4 * (q)]), "+v"((x)[4 * (q) + 1]), "+v"((x)[4 * (q) + 2]), "+v"((x)[4 * (q) + 3]))
 
 /* byte j (0..15, run-time) of the four words of a row quarter */

@@ -18,8 +18,6 @@
 
 namespace mrcz {
 
-/* HT = trees (threads) per workgroup, a template parameter: 1.5 KB of LDS per tree.  48 (74 KB, two workgroups per CU) packs a
- * wave best; 16 (24 KB) leaves LDS room for the streaming kernels of the other compress lanes that run under the trees. */
 constexpr int LELEMS = 286;
 constexpr int BLELEMS = 19;
 constexpr int HSLOTS = 288;
@@ -212,67 +210,7 @@ template <int HT> __device__ __forceinline__ int removed_node(const uint32_t *he
     return (int)((h & 1) ? (w >> 10) & 0x3ffu : w & 0x3ffu);
 }
 
-struct HdrWriter {
-    uint32_t *dst;
-    uint64_t acc;
-    int nacc;
-    uint32_t nwords;
-    uint32_t total;
-};
-__device__ __forceinline__ void hw_put(HdrWriter &h, uint32_t v, int n)
-{
-    h.acc |= (uint64_t)v << h.nacc;
-    h.nacc += n;
-    h.total += (uint32_t)n;
-    if (h.nacc >= 32) {
-        if (h.nwords < (uint32_t)HDRWORDS) h.dst[h.nwords] = (uint32_t)h.acc;
-        h.nwords++;
-        h.acc >>= 32;
-        h.nacc -= 32;
-    }
-}
-__device__ __forceinline__ void hw_finish(HdrWriter &h)
-{
-    if (h.nacc > 0 && h.nwords < (uint32_t)HDRWORDS) h.dst[h.nwords] = (uint32_t)h.acc;
-}
-
 __device__ __forceinline__ uint32_t bit_reverse(uint32_t code, int len) { return __brev(code) >> (32 - len); }
-
-/* zlib's scan_tree / send_tree walk over a sequence of code lengths (trees.c): one step per symbol, given its length and
- * the next symbol's (0xffff behind the last).  A step codes nothing, or 1..3 times the length itself, or a repeat code
- * (16: previous length 3..6 times, 17: 3..10 zeros, 18: 11..138 zeros), or the length once and then code 16.  The 48 trees
- * of a wave are in 48 different states, so the step is written without branches (selects only): both users (counting
- * the bit-length symbols, writing them) run the same instructions for every tree. */
-struct RunScan { int prevlen, count, max_count, min_count; };
-struct RunStep {
-    uint32_t nlit;   /* how many times the length itself is coded here (0..3) */
-    uint32_t rep;    /* 0, or the repeat code that follows (16 / 17 / 18) */
-    uint32_t repcnt; /* the count that code carries */
-};
-__device__ __forceinline__ void run_scan_init(RunScan &r, int firstlen)
-{
-    r.prevlen = -1; r.count = 0;
-    r.max_count = firstlen == 0 ? 138 : 7;
-    r.min_count = firstlen == 0 ? 3 : 4;
-}
-__device__ __forceinline__ RunStep run_scan_step(RunScan &r, int curlen, int nextlen)
-{
-    const int count = r.count + 1;
-    const bool flush = !(count < r.max_count && curlen == nextlen);
-    const bool small = count < r.min_count;
-    const bool lead = curlen != 0 && curlen != r.prevlen; /* a new non-zero length is coded once before it can be repeated */
-    RunStep o;
-    o.nlit = flush ? (small ? (uint32_t)count : (lead ? 1u : 0u)) : 0u;
-    o.rep = (flush && !small) ? (curlen != 0 ? 16u : (count <= 10 ? 17u : 18u)) : 0u;
-    o.repcnt = (uint32_t)(count - (lead ? 1 : 0));
-    r.count = flush ? 0 : count;
-    r.prevlen = flush ? curlen : r.prevlen;
-    const int mx = nextlen == 0 ? 138 : (curlen == nextlen ? 6 : 7);
-    const int mn = (nextlen == 0 || curlen == nextlen) ? 3 : 4;
-    r.max_count = flush ? mx : r.max_count;
-    r.min_count = flush ? mn : r.min_count;
-    return o;
-}
 
 /* RFC 1951 order in which the code-length code lengths are sent */
 __device__ __forceinline__ int bl_order(int i)
@@ -396,12 +334,17 @@ __global__ __launch_bounds__(256) void k_block_index(const StreamInfo *__restric
     if (threadIdx.x == 0) blkbase[nstreams] = carry;
 }
 
-template <int HT, bool FULL> __global__ __launch_bounds__(HT) void k_huffman(const StreamInfo *__restrict__ sinfo, uint32_t nstreams,
-                                                const uint32_t *__restrict__ blkbase, const uint16_t *__restrict__ blkfreq,
-                                                uint32_t *__restrict__ blkcode, uint32_t *__restrict__ blkhdr,
-                                                BlkMeta *__restrict__ meta,
-                                                unsigned long long *__restrict__ dbg /* NULL, or phase clocks: [i] max, [16 + i] sum, [32] trees */)
+/* Trees (threads) per workgroup: 1.5 KB of LDS per tree.  48 (74 KB, two workgroups per CU) packs a wave best. */
+constexpr int HUFF_TREES = 48;
+/* The literal/length and distance codes of every block, one thread per tree: code rows and the block's cost.  The bit-length
+ * tree and the header bits are k_huffman_hdr's.  (sinfo and blkhdr are not read.) */
+__global__ __launch_bounds__(HUFF_TREES) void k_huffman(const StreamInfo *__restrict__ sinfo, uint32_t nstreams,
+                                                        const uint32_t *__restrict__ blkbase, const uint16_t *__restrict__ blkfreq,
+                                                        uint32_t *__restrict__ blkcode, uint32_t *__restrict__ blkhdr,
+                                                        BlkMeta *__restrict__ meta,
+                                                        unsigned long long *__restrict__ dbg /* NULL, or phase clocks: [i] max, [16 + i] sum, [32] trees */)
 {
+    constexpr int HT = HUFF_TREES; /* (the macros above address the tree of this thread) */
     __shared__ TreeMem<HT> tm;
     const int tid = threadIdx.x;
     unsigned long long tp = dbg ? (unsigned long long)clock64() : 0ull;
@@ -435,7 +378,7 @@ template <int HT, bool FULL> __global__ __launch_bounds__(HT) void k_huffman(con
      * The thread is alone on its dependent chain (48 trees a wave, one wave a SIMD), so every phase below is written to
      * wait for memory as seldom as possible: all frequency loads are issued at once, LDS is read in batches of eight
      * independent reads, and counters are bumped with return-less LDS atomics. */
-    int n = 0, max_lcode = -1;
+    int n = 0;
     long static_len = 0, xb_len = 0; /* block cost under the static code / extra bits of the length codes: known from the counts alone */
     for (int g0 = 0; g0 < HROW / 8; g0 += 12) { /* twelve loads in flight (more would only cost registers: a wave of this kernel must
                                                  * still find room on a SIMD that other kernels' waves share) */
@@ -453,7 +396,7 @@ template <int HT, bool FULL> __global__ __launch_bounds__(HT) void k_huffman(con
                 const int xb = sym >= 257 ? len_extra_bits(sym - 257) : 0;
                 static_len += (long)(f * (uint32_t)(static_llen(sym) + xb));
                 if (xb) xb_len += (long)(f * (uint32_t)xb);
-                if (f) { n++; HEAP(n) = (f << 16) | (uint32_t)sym; max_lcode = sym; }
+                if (f) { n++; HEAP(n) = (f << 16) | (uint32_t)sym; }
             }
         }
     }
@@ -550,106 +493,10 @@ template <int HT, bool FULL> __global__ __launch_bounds__(HT) void k_huffman(con
     opt_len += (long)nmatch;
     static_len += 5L * (long)nmatch;
 
-    if (!FULL) { /* the code-length walk, the bit-length tree and the header bits are k_huffman_hdr's (one wave per tree) */
-        BlkMeta mp;
-        mp.opt_len = (uint32_t)opt_len;
-        mp.static_len = (uint32_t)static_len;
-        mp.hdr_bits = 0;
-        mp.eob = eob;
-        meta[(size_t)s * MAXBLK + b] = mp;
-        HPHASE(7);
-        if (dbg) atomicAdd(&dbg[32], 1ull);
-        return;
-    }
-    /* ---------------- bit-length tree (its arrays live in the heap region from here on) ---------------- */
-#pragma unroll
-    for (int i = 0; i < BLELEMS; i++) { BLFREQ(i) = 0; BLLEN(i) = 0; }
-    /* scan_tree over the literal/length lengths [0, max_lcode]; the distance lengths {1, 1} add two to length 1's count */
-    {
-        RunScan rs;
-        uint32_t c16 = 0, c17 = 0, c18 = 0;
-        uint32_t lookahead = LEAFLEN(0);
-        run_scan_init(rs, (int)lookahead);
-        for (int i0 = 0; i0 <= max_lcode; i0 += 8) {
-            uint32_t l[9];
-            l[0] = lookahead;
-#pragma unroll
-            for (int j = 1; j <= 8; j++) l[j] = (i0 + j < HSLOTS) ? LEAFLEN(i0 + j) : 0u;
-            lookahead = l[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const int i = i0 + j;
-                if (i > max_lcode) break;
-                const int curlen = (int)l[j], nextlen = i + 1 <= max_lcode ? (int)l[j + 1] : 0xffff;
-                const RunStep st = run_scan_step(rs, curlen, nextlen);
-                if (st.nlit) atomicAdd(&BLFREQ(curlen), st.nlit);
-                c16 += st.rep == 16u ? 1u : 0u;
-                c17 += st.rep == 17u ? 1u : 0u;
-                c18 += st.rep == 18u ? 1u : 0u;
-            }
-        }
-        BLFREQ(1) += 2u;
-        BLFREQ(16) = c16; BLFREQ(17) = c17; BLFREQ(18) = c18;
-    }
-    HPHASE(5);
-    int bl_max;
-    const int max_blindex = bl_tree_build<HT>(tm, tid, opt_len, bl_max);
-
-    HPHASE(6);
-    /* ---------------- dynamic header bit string (send_all_trees) ---------------- */
-    HdrWriter hw;
-    hw.dst = blkhdr + ((size_t)s * MAXBLK + b) * HDRWORDS;
-    hw.acc = 0; hw.nacc = 0; hw.nwords = 0; hw.total = 0;
-    hw_put(hw, (uint32_t)(max_lcode + 1 - 257), 5);
-    hw_put(hw, 1u /* max_dcode + 1 - 1 */, 5);
-    hw_put(hw, (uint32_t)(max_blindex + 1 - 4), 4);
-    for (int r = 0; r <= max_blindex; r++) {
-        const int o = bl_order(r);
-        hw_put(hw, o <= bl_max ? BLLEN(o) : 0u, 3);
-    }
-    {
-        const uint32_t e16 = BLENT(16), e17 = BLENT(17), e18 = BLENT(18), e1 = BLENT(1);
-        RunScan rs;
-        uint32_t lookahead = LEAFLEN(0);
-        run_scan_init(rs, (int)lookahead);
-        for (int i0 = 0; i0 <= max_lcode; i0 += 8) {
-            uint32_t l[9], ent[8];
-            l[0] = lookahead;
-#pragma unroll
-            for (int j = 1; j <= 8; j++) l[j] = (i0 + j < HSLOTS) ? LEAFLEN(i0 + j) : 0u;
-            lookahead = l[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) ent[j] = BLENT(l[j]); /* eight independent reads: one wait */
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const int i = i0 + j;
-                if (i > max_lcode) break;
-                const int curlen = (int)l[j], nextlen = i + 1 <= max_lcode ? (int)l[j + 1] : 0xffff;
-                const RunStep st = run_scan_step(rs, curlen, nextlen);
-                /* everything this step codes, as one bit string (<= 21 bits) */
-                const uint32_t cc = ent[j] & 0xffu, cl = ent[j] >> 8;
-                const uint32_t lit2 = cc | (cc << cl), lit3 = lit2 | (cc << (2u * cl));
-                const uint32_t lits = st.nlit == 0u ? 0u : (st.nlit == 1u ? cc : (st.nlit == 2u ? lit2 : lit3));
-                const uint32_t lbits = st.nlit * cl;
-                const uint32_t er = st.rep == 16u ? e16 : (st.rep == 17u ? e17 : e18);
-                const uint32_t xbits = st.rep == 16u ? 2u : (st.rep == 17u ? 3u : 7u);
-                const uint32_t xval = st.repcnt - (st.rep == 18u ? 11u : 3u);
-                const uint32_t rl = er >> 8;
-                const uint32_t reps = st.rep ? ((er & 0xffu) | (xval << rl)) : 0u;
-                const uint32_t rbits = st.rep ? rl + xbits : 0u;
-                hw_put(hw, lits | (reps << lbits), (int)(lbits + rbits));
-            }
-        }
-        /* the distance tree's two lengths {1, 1}: a run of two, sent as two literals */
-        hw_put(hw, e1 & 0xffu, (int)(e1 >> 8));
-        hw_put(hw, e1 & 0xffu, (int)(e1 >> 8));
-    }
-    hw_finish(hw);
-
     BlkMeta m;
     m.opt_len = (uint32_t)opt_len;
     m.static_len = (uint32_t)static_len;
-    m.hdr_bits = hw.total;
+    m.hdr_bits = 0;
     m.eob = eob;
     meta[(size_t)s * MAXBLK + b] = m;
     HPHASE(7);
@@ -659,15 +506,15 @@ template <int HT, bool FULL> __global__ __launch_bounds__(HT) void k_huffman(con
 
 
 /* ======================================================================================
- * The dynamic header of one block, ONE WAVE PER TREE (k_huffman<HT, false> leaves the code rows and the literal/length part
- * of the cost): scan_tree, build_bl_tree and send_all_trees (trees.c).  One thread per tree walks the 286 code lengths
- * symbol by symbol, twice, behind a chain of LDS reads -- 0.27 of the 1.19 M cycles of a tree; here the lanes take the
+ * The dynamic header of one block, ONE WAVE PER TREE (k_huffman leaves the code rows and the literal/length part of the
+ * cost): scan_tree, build_bl_tree and send_all_trees (trees.c).  One thread per tree walked the 286 code lengths symbol by
+ * symbol, twice, behind a chain of LDS reads -- 0.27 of the 1.19 M cycles of a tree; here the lanes take the
  * lengths 64 at a time, find the runs of equal lengths with ballots, and every run's codes follow in closed form:
  *   a run of R zeros      = floor(R / 138) x REP18(138), then the rest r: 0 nothing, 1..2 literal zeros, 3..10 REP17(r), else REP18(r)
  *   a run of R lengths L  = c = min(R, 7): c < 4 ? c literals : one literal + REP16(c - 1);   then floor((R - c) / 6) x REP16(6);
  *                           then the rest r: 0 nothing, 1..2 literals, 3..5 REP16(r)
  * (zlib's max_count / min_count state only depends on whether the length repeats or is zero, which a run fixes.)  The tiny
- * bit-length tree itself is built by lane 0 with the same code as the per-thread kernel.
+ * bit-length tree itself is built by lane 0 (bl_tree_build).
  * ==================================================================================== */
 struct RunCodes { uint32_t lits_head, rep_head, full, lits_tail, rep_tail; }; /* codes of one run, in the order they are sent */
 __device__ __forceinline__ RunCodes run_codes(uint32_t L, uint32_t R)

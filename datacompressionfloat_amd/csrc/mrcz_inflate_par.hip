@@ -6,7 +6,7 @@
  * been decoded, so a stream is a sequential chain of ~190 blocks.  The kernels here break that chain speculatively:
  *   k_scan_candidates      every bit position of every payload is tested for the fixed fields of a dynamic block
  *                          header as Z_RLE streams carry them, survivors for a complete code-length code;
- *   k_validate_candidates  one lane per survivor parses the whole header; the decoded code lengths are kept;
+ *   k_validate_wave        one wave per survivor parses the whole header; the decoded code lengths are kept;
  *   k_blk_count            a fixed grid of 512-thread workgroups pulls candidates from a device counter; each decodes
  *                          its block as if it were real, leaves the bytes in a scratch buffer (one piece per window)
  *                          and records where the block ends and what it produced;
@@ -429,11 +429,8 @@ __device__ __noinline__ void tok_table_build(ParShared &sh, int tid, uint32_t my
             sh.tok[idx] = e;
         }
     }
-#ifndef MRCZ_TOK_BY_PATTERN
-#define MRCZ_TOK_BY_PATTERN 1
-#endif
     uint32_t nshort = uni(sh.lit.offs[7]); /* symbols with codes of 1..6 bits: the first ones of the sorted list */
-    if (MRCZ_TOK_BY_PATTERN && uni(sh.lit.offs[4]) != 0u) {
+    if (uni(sh.lit.offs[4]) != 0u) {
         /* A block with codes of 1..3 bits (an exponent plane) has a dozen symbols of 1..6 bits that own nearly the whole table.
          * Symbol after symbol, the workgroup passed a chain of dependent LDS reads per symbol (its place in the sorted list,
          * its length, the first code of that length, then the entries' own distance look-ups): 52 k clocks per block, 15 % of
@@ -789,12 +786,8 @@ __device__ __forceinline__ void staged_copy_out(const ParShared &sh, int tid, co
 }
 
 /* one (generally unaligned) dword store: gfx9 global memory takes unaligned dword accesses */
-#ifndef EXP_NOSTORE
-#define EXP_NOSTORE 0
-#endif
 __device__ __forceinline__ void pk_store4(uint8_t *p, uint32_t w)
 {
-    if (EXP_NOSTORE) { asm volatile("" :: "v"(w), "v"(p)); return; } /* what-if timing builds only: everything but the store itself */
     __builtin_memcpy(p, &w, 4);
 }
 
@@ -1136,7 +1129,7 @@ __device__ __noinline__ void hdr_lengths_block(ParShared &sh, int tid, uint32_t 
 }
 
 /* Decoded dynamic header of one candidate block (row s * MAXCAND + slot of mrcz_ctx::hdrs).  Written by whoever
- * parses the header first -- k_validate_candidates for every scanned candidate, the count pass for a stream's first
+ * parses the header first -- k_validate_wave for every scanned candidate, the count pass for a stream's first
  * block -- and read by the count and write passes, which then go straight to the table build.  `valid` holds a
  * per-call tag mixed with the block's start bit, so rows of earlier calls never match and nothing needs clearing. */
 struct HdrCache {
@@ -1323,13 +1316,9 @@ __device__ __forceinline__ void decode_one_block(ParShared &sh, const StreamView
         return;
     }
     PHASE(14);
-#ifndef EXP_DOUBLE
-#define EXP_DOUBLE 0
-#endif
     const uint32_t mycode = huff_core_litdist(sh, tid);
     PHASE(15);
     PHASE(16);
-    if (EXP_DOUBLE & 4) tok_table_build(sh, tid, mycode); /* what-if timing builds only */
     tok_table_build(sh, tid, mycode);
     tok_pair_pass(sh, tid);
     /* (sh.mintok comes out of tok_table_build; the first window's staging barrier publishes what thread 0 wrote above) */
@@ -1354,10 +1343,6 @@ __device__ __forceinline__ void decode_one_block(ParShared &sh, const StreamView
         uint32_t entry;
         {
             /* P1: exit values of my piece -> my column of sh.ring (rows 0..23 = exit function) */
-            if (EXP_DOUBLE & 1) { /* what-if timing builds only: P1 twice (idempotent) */
-                if (sh.mintok >= 4u) piece_exit_lds<true, false>(sh, (uint32_t)tid, wlead, nw);
-                else piece_exit_lds<false, false>(sh, (uint32_t)tid, wlead, nw);
-            }
             const bool min4 = uni(sh.mintok) >= 4u;
             if (uni(sh.complete)) {
                 if (min4) piece_exit_lds<true, true>(sh, (uint32_t)tid, wlead, nw);
@@ -1373,10 +1358,7 @@ __device__ __forceinline__ void decode_one_block(ParShared &sh, const StreamView
              * broadcast LDS read), which yields the half's and then the wave's exit function.  After the waves'
              * functions are chained (one barrier), pass 2 reads the chain from the now known entry off the lane that followed
              * exactly that entry in pass 1. */
-#ifndef MRCZ_P2_NARROW
-#define MRCZ_P2_NARROW 1
-#endif
-            if (MRCZ_P2_NARROW && uni(sh.nlen) <= 257u) {
+            if (uni(sh.nlen) <= 257u) {
                 /* A block without length codes (HLIT = 257: literals and END_BLOCK only -- nearly every block of a mantissa plane):
                  * a token is one code of at most 15 bits, so a piece is entered at an offset below 16 and FOUR chains of 16
                  * pieces fit the wave's 64 lanes (lane = quarter * 16 + entry offset) where the general form below runs two
@@ -1464,15 +1446,8 @@ __device__ __forceinline__ void decode_one_block(ParShared &sh, const StreamView
         /* P3: walk from the true entry, counting */
         SubResult r;
         const bool dbl = uni(sh.dbl) != 0u; /* (block-uniform) */
-#ifndef MRCZ_STAGED
-#define MRCZ_STAGED 1
-#endif
         /* blocks of long codes keep the bytes their count walk decodes (stage_walk) */
-        const bool staged = MRCZ_STAGED && !dbl && sub <= 37u * uni(sh.mintok); /* (block- and window-uniform) */
-        if ((EXP_DOUBLE & 2) && start != POS_INVALID) { /* what-if timing builds only: one more count walk */
-            const SubResult x = dbl ? count_walk<true, false, true>(sh, start, limit) : count_walk<true>(sh, start, limit);
-            asm volatile("" :: "v"(x.nout), "v"(x.land), "v"(x.lastlit), "v"(x.flags));
-        }
+        const bool staged = !dbl && sub <= 37u * uni(sh.mintok); /* (block- and window-uniform) */
         Staged sg;
         sg.cnt = STG_SLOW; sg.w9 = 0;
         if (staged) {
@@ -1538,10 +1513,6 @@ __device__ __forceinline__ void decode_one_block(ParShared &sh, const StreamView
                 if ((uint32_t)tid == ws.firstlit_tid) sh.lead = op + myoff + bytes_before_first_literal(sh, start, limit, dbl);
             }
         } else wout = sv.out + op + myoff;
-#ifndef EXP_SKIP_P4
-#define EXP_SKIP_P4 0
-#endif
-        if (EXP_SKIP_P4 == 1 || (EXP_SKIP_P4 == 2 && sh.mintok >= 7u) || (EXP_SKIP_P4 == 3 && sh.mintok < 7u)) wout = nullptr; /* what-if timing builds only */
         if (active && r.nout && wout) {
             if (staged && !(sg.cnt & STG_SLOW)) staged_copy_out(sh, tid, sg, wout);
             else if (dbl) write_walk<true>(sh, start, limit, wout, before ? (before & 0xffu) : lastin);
@@ -1743,7 +1714,7 @@ __global__ __launch_bounds__(64) void k_scan_candidates(const uint8_t *__restric
             const uint32_t kraft = acc & 0xfffu, nz = acc >> 12;
             if (kraft != 128u || nz < 2u) continue;
             const uint32_t i = atomicAdd(&sn, 1u);
-            if (i < SURV_CAP) surv[i] = p; /* validated by k_validate_candidates */
+            if (i < SURV_CAP) surv[i] = p; /* validated by k_validate_wave */
         }
         __builtin_amdgcn_wave_barrier(); /* the queue's readers are done before the next step refills it */
         if (sn > SURV_CAP - 64u) flush_survivors(); /* a drain round adds at most 64: never overflows (wave-uniform) */
@@ -1751,10 +1722,7 @@ __global__ __launch_bounds__(64) void k_scan_candidates(const uint8_t *__restric
     flush_survivors();
 }
 
-/* D1b: one lane per signature survivor decodes the whole dynamic header sequentially (from HBM/L2)
- * and keeps the candidate only if the header is fully consistent: the code lengths fill exactly
- * HLIT + HDIST entries, END_BLOCK has a code, and the literal/length code is complete (Kraft sum exactly
- * 1, as every tree zlib builds).  After this test false candidates are practically extinct. */
+/* n bits of the records at bit position `bit`, byte by byte (bytes at or past reclen read as zero) */
 __device__ __forceinline__ uint32_t gbits(const uint8_t *rec, uint64_t reclen, uint64_t bit, int n) /* n <= 16 */
 {
     const uint64_t by = bit >> 3;
@@ -1762,211 +1730,19 @@ __device__ __forceinline__ uint32_t gbits(const uint8_t *rec, uint64_t reclen, u
     for (int k = 0; k < 4; k++) if (by + k < reclen) v |= (uint32_t)rec[by + k] << (8 * k);
     return (v >> (bit & 7u)) & ((1u << n) - 1u);
 }
-constexpr int VH_WORDS = 64; /* header dwords staged per candidate (a dynamic header of this codec is ~100 bytes) */
-__global__ __launch_bounds__(64) void k_validate_candidates(const uint8_t *__restrict__ rec, uint64_t reclen,
-                                                            const DecStream *__restrict__ ds, const uint2 *__restrict__ rawlist,
-                                                            const uint32_t *__restrict__ nraw, uint32_t rawcap,
-                                                            Cand *__restrict__ cands, uint32_t *__restrict__ ncand,
-                                                            HdrCache *__restrict__ hdrs, uint32_t calltag,
-                                                            unsigned long long *__restrict__ dbg /* NULL, or developer stamps: 8 per workgroup for the first 64 */)
-{
-#define VSTAMP(i) do { if (dbg && blockIdx.x < 64u && threadIdx.x == 0) dbg[blockIdx.x * 8u + (i)] = (unsigned long long)clock64(); } while (0)
-    /* One candidate per lane.  A header is ~300 code-length symbols decoded one after the other; reading each from
-     * global memory made this kernel one long chain of dependent HBM/L2 round trips.  Each lane first copies its
-     * candidate's 256 bytes into its own LDS column (64 independent loads), then parses from there. */
-    __shared__ uint32_t hw[VH_WORDS * 64];
-    __shared__ uint8_t vlut[128 * 64];
-    /* decoded code lengths, one ROW per lane (81 dwords: an odd stride, so the lanes' rows start in different banks):
-     * handed to the count / write passes.  Rows are zeroed up front and only non-zero lengths are written, so a run
-     * of zeros -- up to 138 lengths per symbol, and the garbage a false candidate decodes is full of them -- costs
-     * nothing, and the wave does not wait in every step for the lane with the longest run. */
-    constexpr uint32_t VROW = 81;
-    __shared__ uint32_t vlens32[VROW * 64];
-    const int lane = threadIdx.x;
-    uint8_t *vrow = reinterpret_cast<uint8_t *>(vlens32 + VROW * (uint32_t)lane);
-    const uint32_t *rec32 = reinterpret_cast<const uint32_t *>(rec);
-    const uint64_t nrec32 = reclen >> 2;
-    /* the raw list comes in RAW_SEGS segments: flat index -> (segment, offset) through the counts' prefix sums */
-    __shared__ uint32_t segbase[RAW_SEGS + 1];
-    const uint32_t segcap = rawcap / RAW_SEGS;
-    if (lane == 0) {
-        uint32_t acc = 0;
-        for (uint32_t g = 0; g < RAW_SEGS; g++) { segbase[g] = acc; const uint32_t c = nraw[g]; acc += c < segcap ? c : segcap; }
-        segbase[RAW_SEGS] = acc;
-    }
-    __syncthreads();
-    const uint32_t total = segbase[RAW_SEGS];
-    VSTAMP(0);
-    for (uint32_t j = blockIdx.x * 64 + threadIdx.x; j < total; j += gridDim.x * 64) {
-        uint32_t g = 0;
-        for (uint32_t stp = RAW_SEGS / 2; stp; stp >>= 1) if (segbase[g + stp] <= j) g += stp;
-        const uint2 rl = rawlist[(size_t)g * segcap + (j - segbase[g])];
-        const uint32_t s = rl.x, p = rl.y;
-        const DecStream d = ds[s];
-        const uint64_t g0 = d.payoff * 8ull + p;
-        const uint32_t paybits = d.paylen * 8u;
-        const uint64_t wbase = g0 >> 5;
-#pragma unroll 16
-        for (int w = 0; w < VH_WORDS; w++) {
-            const uint64_t wi = wbase + (uint64_t)w;
-            uint32_t v = 0;
-            if (wi < nrec32) v = rec32[wi];
-            else if (wi * 4 < reclen) { /* ragged tail of the records buffer */
-                for (uint64_t k = wi * 4; k < reclen; k++) v |= (uint32_t)rec[k] << (8 * (k - wi * 4));
-            }
-            hw[w * 64 + lane] = v;
-        }
-        VSTAMP(1);
-#pragma unroll
-        for (uint32_t k = 0; k < VROW - 1u; k++) vlens32[VROW * (uint32_t)lane + k] = 0;
-        VSTAMP(2);
-        /* n <= 25 bits at global bit position g: from the lane's LDS column when staged, else from memory */
-        auto gbits = [&](const uint8_t *, uint64_t, uint64_t g, int n) -> uint32_t {
-            const uint64_t q = g - (wbase << 5);
-            const uint32_t i = (uint32_t)(q >> 5);
-            if (i + 1u < (uint32_t)VH_WORDS) {
-                const unsigned long long v = (unsigned long long)hw[i * 64 + lane] | ((unsigned long long)hw[(i + 1u) * 64 + lane] << 32);
-                return (uint32_t)(v >> (q & 31u)) & ((1u << n) - 1u);
-            }
-            return mrcz::gbits(rec, reclen, g, n);
-        };
-        const uint32_t nlen = gbits(rec, reclen, g0 + 3, 5) + 257u, ndist = gbits(rec, reclen, g0 + 8, 5) + 1u;
-        const uint32_t ncode = gbits(rec, reclen, g0 + 13, 4) + 4u;
-        /* code-length code (<= 7 bits): canonical codes -> the lane's private 128-entry table in LDS (sym | len << 5).
-         * Per-length counters are 8-bit fields of one 64-bit register (no dynamically indexed register arrays). */
-        uint32_t bl[19];
-#pragma unroll
-        for (int i = 0; i < 19; i++) bl[i] = 0;
-        unsigned long long cnt = 0;
-        {
-            /* HCLEN + 4 lengths of 3 bits: 57 bits at most, from one 64-bit window */
-            const uint64_t q = g0 + 17 - (wbase << 5);
-            const uint32_t i0 = (uint32_t)(q >> 5), sh0 = (uint32_t)q & 31u;
-            const uint32_t a0 = hw[i0 * 64 + lane], a1 = hw[(i0 + 1u) * 64 + lane], a2 = hw[(i0 + 2u) * 64 + lane];
-            const unsigned long long lo = ((unsigned long long)a0 | ((unsigned long long)a1 << 32)) >> sh0;
-            const unsigned long long hi = sh0 ? ((unsigned long long)a2 << (64u - sh0)) : 0ull;
-            const unsigned long long bits = lo | hi;
-#pragma unroll
-            for (int i = 0; i < 19; i++) {
-                if ((uint32_t)i < ncode) {
-                    const uint32_t l = (uint32_t)(bits >> (3 * i)) & 7u;
-                    bl[k_bl_order(i)] = l;
-                    cnt += 1ull << (8u * l);
-                }
-            }
-        }
-        unsigned long long next = 0; /* next code of each length */
-        uint32_t blkraft = 0;
-        {
-            uint32_t code = 0;
-#pragma unroll
-            for (int l = 1; l <= 7; l++) {
-                const uint32_t cprev = l == 1 ? 0u : (uint32_t)(cnt >> (8 * (l - 1))) & 0xffu;
-                code = (code + cprev) << 1;
-                next |= (unsigned long long)(code & 0xffu) << (8 * l);
-                blkraft += ((uint32_t)(cnt >> (8 * l)) & 0xffu) << (7 - l);
-            }
-        }
-        bool ok = nlen <= 286u && ndist <= 30u && blkraft == 128u; /* complete code: every table entry gets written */
-        if (ok) {
-#pragma unroll
-            for (int sym = 0; sym < 19; sym++) {
-                const uint32_t l = bl[sym];
-                if (l) {
-                    const uint32_t c = (uint32_t)(next >> (8u * l)) & 0xffu;
-                    next += 1ull << (8u * l);
-                    const uint32_t r = __brev(c) >> (32u - l);
-                    for (uint32_t k = r; k < 128u; k += 1u << l) vlut[k * 64u + (uint32_t)lane] = (uint8_t)((uint32_t)sym | (l << 5));
-                }
-            }
-        }
-        VSTAMP(3);
-        const uint32_t total_l = nlen + ndist;
-        uint32_t idx = 0, kraft = 0, prev = 0, eoblen = 0;
-        /* The symbols: a 64-bit bit buffer refilled from the lane's LDS column (the refill address only depends on how
-         * many words were taken, so it is off the dependent chain: one table read per symbol is what a step waits for). */
-        const uint64_t q0 = g0 + 17 + 3ull * ncode - (wbase << 5); /* bit inside the staged words */
-        uint32_t wi = (uint32_t)(q0 >> 5);
-        uint32_t used = (uint32_t)q0;                                /* bits consumed, relative to the staged words */
-        unsigned long long buf = 0;
-        int nb = 0;
-        if (wi + 1u < (uint32_t)VH_WORDS) {
-            buf = ((unsigned long long)hw[wi * 64 + lane] | ((unsigned long long)hw[(wi + 1u) * 64 + lane] << 32)) >> (used & 31u);
-            nb = 64 - (int)(used & 31u);
-            wi += 2;
-        } else ok = false; /* (cannot happen: the code-length code ends inside the first four words) */
-        const uint32_t pay_end = paybits - p; /* bits from the candidate's start to the end of the payload */
-        const uint32_t used0 = (uint32_t)(g0 - (wbase << 5));
-        /* Straight-line steps: a wave is alone on its SIMD here, so what a step costs is its instruction count, and with one
-         * candidate per lane every branch a lane takes is paid by all 64.  All state changes are selects on `go`; the loop
-         * runs until no lane is parsing.  The lengths of a step go out as six byte stores (a non-zero length repeats at most
-         * six times; the bytes behind the run are still zero and are written as zero). */
-        bool act = ok;
-        for (;;) {
-            act = act && idx < total_l;
-            if (!__any(act)) break;
-            const bool need = nb < 32;
-            uint32_t w = hw[(wi < (uint32_t)VH_WORDS ? wi : (uint32_t)VH_WORDS - 1u) * 64 + lane];
-            if (act && need && wi >= (uint32_t)VH_WORDS) /* a header longer than the staged 256 bytes: from memory */
-                w = (uint32_t)mrcz::gbits(rec, reclen, (wbase + wi) << 5, 16) | ((uint32_t)mrcz::gbits(rec, reclen, ((wbase + wi) << 5) + 16, 16) << 16);
-            buf |= need ? ((unsigned long long)w << nb) : 0ull;
-            nb += need ? 32 : 0;
-            wi += need ? 1u : 0u;
-            bool go = act && used - used0 + 14u <= pay_end;
-            const uint32_t v = (uint32_t)buf & 0x3fffu;
-            const uint32_t e = vlut[(v & 127u) * 64u + (uint32_t)lane];
-            const uint32_t l = e >> 5, sym = e & 31u;
-            const bool is16 = sym == 16u, is17 = sym == 17u, is18 = sym == 18u;
-            const uint32_t nex = is18 ? 7u : is17 ? 3u : is16 ? 2u : 0u;
-            const uint32_t rep = sym < 16u ? 1u : (is18 ? 11u : 3u) + ((v >> l) & ((1u << nex) - 1u));
-            const uint32_t val = sym < 16u ? sym : is16 ? prev : 0u;
-            const uint32_t take = l + nex;
-            go = go && !(is16 && idx == 0u) && idx + rep <= total_l;
-            /* the lengths at [idx, idx + rep) that belong to the literal/length code */
-            const uint32_t lo = idx < nlen ? idx : nlen, hi = idx + rep < nlen ? idx + rep : nlen;
-            const uint32_t kr = kraft + (val ? (hi - lo) * (32768u >> val) : 0u);
-            go = go && kr <= 32768u; /* over-subscribed: no code */
-#pragma unroll
-            for (uint32_t k = 0; k < 6u; k++) vrow[idx + k] = (uint8_t)((go && k < rep) ? val : 0u);
-            kraft = go ? kr : kraft;
-            eoblen = (go && lo <= 256u && 256u < hi) ? val : eoblen;
-            buf >>= go ? take : 0u;
-            nb -= go ? (int)take : 0;
-            used += go ? take : 0u;
-            idx += go ? rep : 0u;
-            prev = go ? val : prev;
-            ok = ok && (go || !act);
-            act = go;
-        }
-        VSTAMP(4);
-        if (ok && kraft == 32768u && eoblen != 0u) {
-            const uint32_t i = atomicAdd(&ncand[s], 1u);
-            if (i < (uint32_t)MAXCAND) {
-                Cand cnd; cnd.bit = p; cnd.end = 0; cnd.nout = 0; cnd.info = 0; cands[(size_t)s * MAXCAND + i] = cnd;
-                HdrCache *hc = hdrs + ((size_t)s * MAXCAND + i);
-                uint32_t *dst = reinterpret_cast<uint32_t *>(hc->lens);
-                for (uint32_t k = 0; k < (total_l + 3u) / 4u; k++) dst[k] = vlens32[VROW * (uint32_t)lane + k]; /* (lengths behind total_l are zero) */
-                hc->bfinal = 0; hc->nlen = nlen; hc->ndist = ndist;
-                hc->cur_after = p + (used - used0);
-                hc->valid = hdr_tag(calltag, p);
-            }
-        }
-        VSTAMP(5);
-    }
-    VSTAMP(6);
-#undef VSTAMP
-}
 
-/* D1b, one WAVE per survivor.  The per-lane version above is as long as its slowest lane: ~300 code-length symbols one
- * after the other at ~800 clocks each (a wave alone on its SIMD issues an instruction every five clocks or so), 150 us
- * per call however few candidates there are.  Here the 64 lanes share one header:
+/* D1b, one WAVE per signature survivor decodes the whole dynamic header and keeps the candidate only if the header is fully
+ * consistent: the code lengths fill exactly HLIT + HDIST entries, END_BLOCK has a code, and the literal/length code is
+ * complete (Kraft sum exactly 1, as every tree zlib builds).  After this test false candidates are practically extinct.
+ * One LANE per survivor was as long as its slowest lane: ~300 code-length symbols one after the other at ~800 clocks each
+ * (a wave alone on its SIMD issues an instruction every five clocks or so), 150 us per call however few candidates there
+ * are.  Here the 64 lanes share one header:
  *   - the header's 256 bytes are one coalesced load; the code-length code's table is filled by its 19 symbols at once;
  *   - a round looks at 64 consecutive bit positions: every lane decodes the symbol that WOULD start at its bit, then the
  *     positions where symbols really start are found by hopping from symbol to symbol with scalar lane reads (two per
  *     symbol), and everything else -- run values behind "repeat previous", positions in the length array by a prefix sum,
  *     the Kraft sum, the stores -- is done by the marked lanes together;
- *   - false candidates decode noise, whose zero runs reach HLIT + HDIST lengths within two or three rounds.
- * The accepted candidates and their HdrCache rows are the same as the per-lane kernel's (same tests), in another order. */
+ *   - false candidates decode noise, whose zero runs reach HLIT + HDIST lengths within two or three rounds. */
 /* record words one wave stages at a time: 128 bytes.  Headers of this codec are 100-160 bytes, so the window is moved up once
  * for about every other candidate -- that path is part of every test run, not a corner case. */
 constexpr int VW_WORDS = 32;
@@ -2187,7 +1963,7 @@ __global__ __launch_bounds__(PT) __attribute__((amdgpu_waves_per_eu(6, 6))) void
                                                   const uint32_t *__restrict__ candbase, const uint32_t *__restrict__ jobord, Cand *__restrict__ cands,
                                                   uint8_t *__restrict__ scratch, uint32_t *__restrict__ scratch_top, uint32_t scratch_cap16,
                                                   HdrCache *__restrict__ hdrs, uint32_t calltag, uint32_t *__restrict__ jobctr,
-                                                  unsigned long long *__restrict__ dbg, uint32_t use_hint)
+                                                  unsigned long long *__restrict__ dbg)
 {
     /* static LDS (below the 64 KiB static limit): the compiler folds the structure's address into the instructions' offset
      * fields; with a dynamic allocation every LDS access of the hot loops paid an extra address add */
@@ -2221,7 +1997,6 @@ __global__ __launch_bounds__(PT) __attribute__((amdgpu_waves_per_eu(6, 6))) void
                 if (b > mybit && b < m) m = b;
             }
             hint = uni(block_min_pt<false>(m, sh.scan_a)); /* (its barrier also publishes the lines above; scan_a is next written behind the block's first barriers) */
-            if (!use_hint) hint = 0xffffffffu;
         }
         ScratchOut so;
         so.base = scratch; so.top = scratch_top; so.cap16 = scratch_cap16; so.wbase = c->wbase; so.wlen = c->wlen;

@@ -233,7 +233,9 @@ int64_t mrcz_debug_chain_fallbacks(mrcz_ctx_t *ctx); /* streams of the last unco
 int mrcz_debug_inflate_phases(mrcz_ctx_t *ctx, int enable, uint32_t stream, uint64_t out[20]);
 /* (enable = 3 switches on the phase clocks of the Huffman construction kernel instead: out[0..7] of stream 0 = the slowest
  * tree's clocks per phase, out[16..19] of stream 0 and out[0..3] of stream 1 = their sums, out[12] of stream 1 = trees;
- * tests/tools_huff_profile.py prints them.) */
+ * tests/tools_huff_profile.py prints them.  enable = 4 switches on k_chain's shader-clock stamps instead: 8 per stream, stream
+ * s's at flat counter 8 s (out of `stream` k holds flat counters 20 k .. 20 k + 19); tools/jobs/chain_validate_phases.py
+ * prints them.) */
 
 /* Inspection (profiling): block-start candidates of the last batch of the last mrcz_uncompress_chunks call:
  * out[0] = positions that passed the signature scan and went to header validation, out[1] = validated candidates. */

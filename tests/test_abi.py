@@ -47,6 +47,13 @@ def test_library_is_gfx950_only(built):
         assert targets and all("gfx950" in t for t in targets), targets
 
 
+def test_library_reads_no_tuning_environment(built):
+    # the device library reads two environment variables: a diagnostic and a test knob.  Tuning choices are constants in the
+    # source; experiments build another library and load it through MRCZ_LIB_PATH.
+    names = set(m.decode() for m in re.findall(rb"MRCZ_[A-Z0-9_]+", open(built, "rb").read()))
+    assert names <= {"MRCZ_TRACE", "MRCZ_SCRATCH_BYTES"}, sorted(names)
+
+
 def test_bound_is_pure_host_arithmetic(built):
     lib = ctypes.CDLL(built)
     lib.mrcz_records_bound.restype = ctypes.c_uint64
