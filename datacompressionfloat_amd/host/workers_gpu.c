@@ -5,9 +5,9 @@
  * time (fread -> mask/split -> 4 x deflate -> fwrite, workers.c:779-855); here a file flows through a
  * three-stage pipeline whose stages all run at once:
  *
- *   reader thread   fread one chunk into a pinned ring slot, enqueue its host->device copy (upload stream)
+ *   reader thread   copy one chunk into a pinned ring slot, enqueue its host->device copy (upload stream)
  *   caller thread   when the chunks of a batch are on their way, enqueue the codec kernels (compute stream)
- *   writer thread   device->host copy of the batch's result in slices (download stream), fwrite in order
+ *   writer thread   device->host copy of the batch's result in slices (download stream), a sink thread writes them in order
  *
  * with two device batch buffers per direction, so batch k+1 is uploaded and batch k-1 downloaded while
  * batch k is coded.  Ordering is done with the events of include/mrcz_hip.h; the host only blocks on the
@@ -37,10 +37,6 @@ int isTestThroughput = 0; /* src/core/workers.c:39 */
 #define R_IN 4                    /* pinned input ring: chunk-sized slots */
 #define R_OUT 6                   /* pinned output ring */
 #define OUT_SLOT (16u << 20)      /* bytes per output slice */
-#define MAXWRITERS 8
-#define NWRITERS 1                /* threads that pwrite() finished slices.  ONE: tmpfs (and the page cache) serialise the writers of a file on its inode
-                                   * lock, and contending for it is worse than not having it -- tools/shm_write_probe.c on the MI355X box: one thread
-                                   * 8.4 GB/s, two to sixteen threads 3.5-3.8 GB/s into the same file, a MAP_SHARED mapping filled by 4-16 threads 5.6-7.6 */
 #define CHUNK_BYTES ((uint64_t)CHUNK_SIZE * 4u)
 #define IN_SLOT (CHUNK_BYTES + 64u) /* a chunk of floats, or a chunk record (16-byte header + <= 4 RAW planes) */
 
@@ -67,7 +63,7 @@ static int batch_chunks(void) /* MRCZ_BATCH_CHUNKS overrides the default (tests:
 }
 
 /* Fatal errors end the process the way the reference's do (exit(-1), workers.c:708-712) -- but die() is called from the reader,
- * writer and pwrite threads while the other threads of the pipeline are still enqueuing copies on the session's buffers and
+ * writer and sink threads while the other threads of the pipeline are still enqueuing copies on the session's buffers and
  * events: running exit handlers (sessions_release_all, the HIP runtime's destructors) under them frees what they use.  So the
  * flag stops the session teardown, stdio is flushed by hand and the process leaves through _exit with the reference's status
  * (exit(-1) = 255). */
@@ -305,13 +301,13 @@ typedef struct {
     uint64_t nbatches;
     int crowd;            /* pipelines in flight when this one started (itself included) */
     double gpu_time;      /* time the writer spent waiting for coded batches (what the reference counts as zip/unzip time) */
-    double t_fread, t_slotwait, t_fwrite, t_d2hwait, t_setup; /* MRCZ_TRACE=1: where the wall time of the call went */
-    /* output: slices of the result are written at their file offsets by NWRITERS threads (pwrite); fd_out < 0 = the output
-     * cannot seek, the writer thread fwrite()s the slices itself, in order */
+    double t_copyin, t_slotwait, t_sinkwait, t_d2hwait, t_setup; /* MRCZ_TRACE=1: where the wall time of the call went */
+    /* output: the sink thread writes the slices of the result in file order, with pwrite() at their file offsets on fd_out, or
+     * with fwrite() on fout when the output cannot seek (fd_out < 0) */
     int fd_out;
     uint64_t out_off;                 /* file offset of the next result byte */
     struct { int slot; uint64_t off, len; } wq[R_OUT];
-    int wq_head, wq_tail;             /* slices handed to the pwrite threads: [head, tail) */
+    int wq_head, wq_tail;             /* slices handed to the sink: [head, tail) */
     int slot_busy[R_OUT];
     int wq_done;                      /* no slice follows */
     pthread_mutex_t wmu;
@@ -321,15 +317,14 @@ typedef struct {
 static void trace_report(const pipe_t *p, const char *what, double elapsed, uint64_t bytes)
 {
     if (!getenv("MRCZ_TRACE")) return;
-    fprintf(stderr, "[mrcz trace] %s: %.4f s (%.2f GB/s of floats), setup %.4f, reader: fread %.4f + slot waits %.4f, writer: waits for the codec %.4f, "
-            "copy-back waits %.4f, fwrite %.4f, batches %llu of %d chunks\n", what, elapsed, (double)bytes / elapsed / 1e9, p->t_setup, p->t_fread,
-            p->t_slotwait, p->gpu_time, p->t_d2hwait, p->t_fwrite, (unsigned long long)p->nbatches, p->batch_chunks);
+    fprintf(stderr, "[mrcz trace] %s: %.4f s (%.2f GB/s of floats), setup %.4f, reader: copy in %.4f + slot waits %.4f, writer: waits for the codec %.4f, "
+            "for the sink %.4f, sink: copy-back waits %.4f, batches %llu of %d chunks\n", what, elapsed, (double)bytes / elapsed / 1e9, p->t_setup,
+            p->t_copyin, p->t_slotwait, p->gpu_time, p->t_sinkwait, p->t_d2hwait, (unsigned long long)p->nbatches, p->batch_chunks);
 }
 
 /* A chunk goes from the page cache (the input mapping) into a pinned ring slot with NFILL threads, each copying a third of
  * it (one thread moves 6-8 GB/s out of the page cache, the host->device copy from pinned memory ~50 GB/s and asynchronous; a
- * copy straight from the pageable mapping, which the runtime stages itself, moves ~8 GB/s and blocks the reader).
- * MRCZ_FILLERS=0 keeps the direct copy from the mapping. */
+ * copy straight from the pageable mapping, which the runtime stages itself, moved ~8 GB/s and blocked the reader). */
 #define NFILL 3
 typedef struct {
     pthread_t th[NFILL - 1];
@@ -342,7 +337,7 @@ typedef struct {
     const unsigned char *src;
     uint64_t bytes;
     int started;
-    int nthreads;          /* 1..NFILL copy threads, the caller included (MRCZ_FILLERS) */
+    int nthreads;          /* 1..NFILL copy threads, the caller included */
 } fillpool_t;
 typedef struct { fillpool_t *fp; int part; } fillarg_t;
 static void fill_part(const fillpool_t *fp, int part)
@@ -403,21 +398,41 @@ static void fill_stop(fillpool_t *fp)
     pthread_cond_destroy(&fp->cv);
 }
 
-/* The input file as one read-only mapping, if it can be mapped (a regular file): its pages go from the page cache to the
- * device with no copy into a staging buffer in between (fread into pinned memory moves ~6-8 GB/s per thread; the
- * host->device copy straight from the mapping ~18 GB/s on first touch).  NULL = use the fread ring. */
-static const unsigned char *map_input(FILE *f, uint64_t *pos, uint64_t *size)
+/* Where the reader's bytes come from: the input file as one read-only mapping, copied into the ring by the filler pool, or
+ * fread when the input cannot be mapped (not a regular file: a pipe) */
+typedef struct {
+    FILE *f;
+    const unsigned char *map; /* NULL = fread */
+    uint64_t pos, size;       /* mapping: offset of the next byte, length of the file */
+    fillpool_t fp;
+    fillarg_t fa[NFILL - 1];
+} source_t;
+static void source_open(source_t *in, FILE *f, int nfill)
 {
-    if (getenv("MRCZ_NO_MMAP")) return NULL;
+    memset(in, 0, sizeof(*in));
+    in->f = f;
+    in->fp.nthreads = nfill;
     const int fd = fileno(f);
     struct stat st;
     const long at = ftell(f);
-    if (fd < 0 || at < 0 || fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size <= 0) return NULL;
-    void *m = mmap(NULL, (size_t)st.st_size, PROT_READ, MAP_SHARED | (getenv("MRCZ_MMAP_POPULATE") ? MAP_POPULATE : 0), fd, 0);
-    if (m == MAP_FAILED) return NULL;
-    *pos = (uint64_t)at;
-    *size = (uint64_t)st.st_size;
-    return (const unsigned char *)m;
+    if (fd < 0 || at < 0 || fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size <= 0) return;
+    void *m = mmap(NULL, (size_t)st.st_size, PROT_READ, MAP_SHARED, fd, 0);
+    if (m == MAP_FAILED) return;
+    in->map = (const unsigned char *)m;
+    in->pos = (uint64_t)at;
+    in->size = (uint64_t)st.st_size;
+}
+/* the next `bytes` of the input into `dst`; `what` is the error when the input ends first */
+static void source_read(source_t *in, unsigned char *dst, uint64_t bytes, const char *what)
+{
+    if (!in->map) {
+        if (fread(dst, 1, (size_t)bytes, in->f) != bytes) die(what, NULL);
+        return;
+    }
+    if (in->pos + bytes > in->size) die(what, NULL);
+    if (bytes <= 4096) memcpy(dst, in->map + in->pos, (size_t)bytes); /* (a chunk header: not worth waking the pool for) */
+    else fill_copy(&in->fp, in->fa, dst, in->map + in->pos, bytes);
+    in->pos += bytes;
 }
 
 static void *reader_main(void *arg)
@@ -426,14 +441,8 @@ static void *reader_main(void *arg)
     session_t *s = p->s;
     const uint64_t nd = (uint64_t)p->nd, inflight = 2u * nd;
     uint64_t chunk = 0, k = 0, done_floats = 0;
-    uint64_t mpos = 0, msize = 0;
-    const unsigned char *map = map_input(p->fin, &mpos, &msize);
-    const int fillers = map && !(getenv("MRCZ_FILLERS") && atoi(getenv("MRCZ_FILLERS")) == 0); /* mapping -> pinned ring -> device */
-    fillpool_t fp;
-    fillarg_t fa[NFILL - 1];
-    memset(&fp, 0, sizeof(fp));
-    fp.nthreads = p->crowd > 2 ? 1 : (p->crowd == 2 ? 2 : NFILL); /* several files at once (mrc_tarx -n): their threads are the parallelism */
-    if (getenv("MRCZ_FILLERS")) { const int v = atoi(getenv("MRCZ_FILLERS")); if (v >= 1 && v <= NFILL) fp.nthreads = v; }
+    source_t in;
+    source_open(&in, p->fin, p->crowd > 2 ? 1 : (p->crowd == 2 ? 2 : NFILL)); /* several files at once (mrc_tarx -n): their threads are the parallelism */
     int eof = 0;
     while (!eof) {
         const int di = (int)(k % nd), b = (int)((k / nd) & 1u), qi = 2 * di + b;
@@ -453,43 +462,27 @@ static void *reader_main(void *arg)
             if (done_floats >= p->total_floats) { eof = 1; break; }
             const uint64_t left = p->total_floats - done_floats;
             const uint64_t nfl = left < p->chk ? left : p->chk; /* floats of this chunk */
-            const unsigned char *h;
-            unsigned char *ring = NULL;
-            int slot = 0;
+            const int slot = (int)(chunk % R_IN);
             double tt = now_sec();
-            if (!map || fillers) {
-                slot = (int)(chunk % R_IN);
-                if (chunk >= R_IN) { /* the slot's previous upload (possibly to another device) is done */
-                    devses_t *P = &s->d[s->in_dev[slot]];
-                    CK(mrcz_event_sync(P->e->c, P->in_ev[slot]), "event sync", P->e->c);
-                }
-                p->t_slotwait += now_sec() - tt;
-                tt = now_sec();
-                if (!s->h_in[slot]) CK(mrcz_host_malloc(c, &s->h_in[slot], IN_SLOT), "fail to alloc mem", c);
-                ring = (unsigned char *)s->h_in[slot];
+            if (chunk >= R_IN) { /* the slot's previous upload (possibly to another device) is done */
+                devses_t *P = &s->d[s->in_dev[slot]];
+                CK(mrcz_event_sync(P->e->c, P->in_ev[slot]), "event sync", P->e->c);
             }
-            uint64_t bytes = 0;
+            p->t_slotwait += now_sec() - tt;
+            tt = now_sec();
+            if (!s->h_in[slot]) CK(mrcz_host_malloc(c, &s->h_in[slot], IN_SLOT), "fail to alloc mem", c);
+            unsigned char *ring = (unsigned char *)s->h_in[slot];
+            uint64_t bytes;
             if (!p->decode) {
                 /* one chunk of floats (workers.c:744,854) */
                 bytes = nfl * 4u;
-                if (map) {
-                    if (mpos + bytes > msize) die("input file shrank while it was read", NULL);
-                    h = map + mpos;
-                    if (fillers) { fill_copy(&fp, fa, ring, h, bytes); h = ring; }
-                } else {
-                    if (fread(ring, sizeof(uint32_t), (size_t)nfl, p->fin) != nfl) die("input file shrank while it was read", NULL);
-                    h = ring;
-                }
+                source_read(&in, ring, bytes, "input file shrank while it was read");
             } else {
                 /* one chunk record: the 16-byte header (workers.c:52-69, unpack_header zip.c:393-399), then the four payloads */
-                unsigned char hd16[16];
-                if (map) {
-                    if (mpos + 16 > msize) die("truncated container (chunk header)", NULL);
-                    memcpy(hd16, map + mpos, 16);
-                } else if (fread(hd16, 1, 16, p->fin) != 16) die("truncated container (chunk header)", NULL);
+                source_read(&in, ring, 16, "truncated container (chunk header)");
                 uint64_t pay = 0;
                 for (int j = 0; j < 4; j++) {
-                    const uint64_t l = (uint64_t)hd16[4 * j] | ((uint64_t)hd16[4 * j + 1] << 8) | ((uint64_t)hd16[4 * j + 2] << 16) | ((uint64_t)(hd16[4 * j + 3] & 0x7f) << 24);
+                    const uint64_t l = (uint64_t)ring[4 * j] | ((uint64_t)ring[4 * j + 1] << 8) | ((uint64_t)ring[4 * j + 2] << 16) | ((uint64_t)(ring[4 * j + 3] & 0x7f) << 24);
                     p->plane_z[j] += l;
                     pay += l;
                 }
@@ -497,26 +490,17 @@ static void *reader_main(void *arg)
                 /* the largest record the reference's writer can emit: a plane that does not shrink is stored RAW (zip.c:177-190),
                  * so four RAW planes of this chunk's floats; anything longer would also overrun the device batch buffer */
                 if (bytes > 16u + 4u * nfl || bytes > IN_SLOT) die("chunk record larger than a chunk of RAW planes", NULL);
-                if (map) {
-                    if (mpos + bytes > msize) die("truncated container (payload)", NULL);
-                    h = map + mpos;
-                    if (fillers) { fill_copy(&fp, fa, ring, h, bytes); h = ring; }
-                } else {
-                    memcpy(ring, hd16, 16);
-                    if (fread(ring + 16, 1, (size_t)pay, p->fin) != pay) die("truncated container (payload)", NULL);
-                    h = ring;
-                }
+                source_read(&in, ring + 16, pay, "truncated container (payload)");
                 p->zbytes += bytes;
             }
             bt.units += nfl;
             done_floats += nfl;
-            mpos += bytes;
             if (done_floats >= p->total_floats) eof = 1;
-            if (!map || fillers) p->t_fread += now_sec() - tt;
+            p->t_copyin += now_sec() - tt;
             if (off + bytes > D->d_a_cap) die("batch larger than its device buffer", NULL);
-            CK(mrcz_copy_h2d_async(c, MRCZ_STREAM_UPLOAD, (char *)D->d_a[b] + off, h, bytes), "H2D copy", c);
-            if (map && !fillers) p->t_fread += now_sec() - tt; /* a copy from pageable memory returns when the source has been consumed */
-            else { CK(mrcz_event_record(c, MRCZ_STREAM_UPLOAD, D->in_ev[slot]), "event record", c); s->in_dev[slot] = di; }
+            CK(mrcz_copy_h2d_async(c, MRCZ_STREAM_UPLOAD, (char *)D->d_a[b] + off, ring, bytes), "H2D copy", c);
+            CK(mrcz_event_record(c, MRCZ_STREAM_UPLOAD, D->in_ev[slot]), "event record", c);
+            s->in_dev[slot] = di;
             off += bytes;
             chunk++;
         }
@@ -531,17 +515,16 @@ static void *reader_main(void *arg)
         pthread_mutex_unlock(&p->mu);
         k++;
     }
-    fill_stop(&fp);
-    if (map) {
-        /* the mapping may only go away once every copy out of it is done (a copy from pageable memory is normally complete when
-         * the call returns; the event makes it certain) */
+    fill_stop(&in.fp);
+    if (in.map) {
+        /* the mapping goes away once every upload of the call is done */
         for (int di = 0; di < p->nd; di++) {
             devses_t *D = &s->d[di];
             CK(mrcz_event_record(D->e->c, MRCZ_STREAM_UPLOAD, D->in_ev[0]), "event record", D->e->c);
             CK(mrcz_event_sync(D->e->c, D->in_ev[0]), "event sync", D->e->c);
         }
-        munmap((void *)map, (size_t)msize);
-        if (p->decode) fseek(p->fin, (long)mpos, SEEK_SET); /* leave the stream where fread would have left it */
+        munmap((void *)in.map, (size_t)in.size);
+        if (p->decode) fseek(p->fin, (long)in.pos, SEEK_SET); /* leave the stream where fread would have left it */
     }
     pthread_mutex_lock(&p->mu);
     p->reader_eof = 1;
@@ -550,7 +533,11 @@ static void *reader_main(void *arg)
     return NULL;
 }
 
-static void *pwrite_main(void *arg)
+/* The sink: ONE thread per file writes the slices in file order.  One, because tmpfs (and the page cache) serialise the
+ * writers of a file on its inode lock, and contending for it is worse than not having it -- tools/shm_write_probe.c on the
+ * MI355X box: one thread 8.4 GB/s, two to sixteen threads 3.5-3.8 GB/s into the same file, a MAP_SHARED mapping filled by
+ * 4-16 threads 5.6-7.6. */
+static void *sink_main(void *arg)
 {
     pipe_t *p = (pipe_t *)arg;
     session_t *s = p->s;
@@ -563,15 +550,20 @@ static void *pwrite_main(void *arg)
         const uint64_t off = p->wq[i].off, len = p->wq[i].len;
         p->wq_head++;
         pthread_mutex_unlock(&p->wmu);
+        const double tt = now_sec();
         {
             devses_t *D = &s->d[s->out_dev[slot]]; /* (set before the slice was queued, under wmu) */
             CK(mrcz_event_sync(D->e->c, D->out_ev[slot]), "event sync", D->e->c);
         }
-        uint64_t done = 0;
-        while (done < len) {
-            const ssize_t w = pwrite(p->fd_out, (const char *)s->h_out[slot] + done, (size_t)(len - done), (off_t)(off + done));
-            if (w <= 0) die("pwrite", NULL);
-            done += (uint64_t)w;
+        p->t_d2hwait += now_sec() - tt;
+        if (p->fd_out < 0) {
+            if (fwrite(s->h_out[slot], 1, (size_t)len, p->fout) != len) die("fwrite", NULL); /* workers.c:837-850 / 627,668 */
+        } else {
+            for (uint64_t done = 0; done < len;) {
+                const ssize_t w = pwrite(p->fd_out, (const char *)s->h_out[slot] + done, (size_t)(len - done), (off_t)(off + done));
+                if (w <= 0) die("pwrite", NULL);
+                done += (uint64_t)w;
+            }
         }
         pthread_mutex_lock(&p->wmu);
         p->slot_busy[slot] = 0;
@@ -587,15 +579,12 @@ static void *writer_main(void *arg)
     session_t *s = p->s;
     const uint64_t nd = (uint64_t)p->nd;
     uint64_t oslice = 0; /* output ring position */
-    pthread_t pw[MAXWRITERS];
-    int nwr = NWRITERS;
-    if (getenv("MRCZ_WRITERS")) { const int v = atoi(getenv("MRCZ_WRITERS")); if (v >= 1 && v <= MAXWRITERS) nwr = v; }
-    const int par = p->fd_out >= 0 && isTestThroughput != 1;
-    if (par) {
+    pthread_t sink;
+    const int writes = isTestThroughput != 1; /* -d 1: the codec runs, nothing is written (workers.c:39) */
+    if (writes) {
         pthread_mutex_init(&p->wmu, NULL);
         pthread_cond_init(&p->wcv, NULL);
-        for (int i = 0; i < nwr; i++)
-            if (pthread_create(&pw[i], NULL, pwrite_main, p) != 0) die("pthread_create", NULL);
+        if (pthread_create(&sink, NULL, sink_main, p) != 0) die("pthread_create", NULL);
     }
     for (uint64_t k = 0;; k++) {
         const int di = (int)(k % nd), b = (int)((k / nd) & 1u), qi = 2 * di + b;
@@ -618,58 +607,31 @@ static void *writer_main(void *arg)
             if (D->h_res[b][1] != 0 || D->h_res[b][0] != bt.in_bytes) die("uncompress: malformed chunk records or deflate stream", NULL);
             out_bytes = bt.units * 4u;
         }
-        const uint64_t nsl = (out_bytes + OUT_SLOT - 1) / OUT_SLOT;
-        if (isTestThroughput == 1 || nsl == 0) CK(mrcz_event_record(c, MRCZ_STREAM_DOWNLOAD, D->down_ev[b]), "event record", c);
-        else if (par) {
-            /* every slice: wait for a free ring slot, start its copy, hand it to the pwrite threads */
-            for (uint64_t j = 0; j < nsl; j++) {
-                const int os = (int)((oslice + j) % R_OUT);
-                double tt = now_sec();
-                pthread_mutex_lock(&p->wmu);
-                while (p->slot_busy[os]) pthread_cond_wait(&p->wcv, &p->wmu);
-                p->slot_busy[os] = 1;
-                pthread_mutex_unlock(&p->wmu);
-                p->t_fwrite += now_sec() - tt;
-                if (!s->h_out[os]) CK(mrcz_host_malloc(c, &s->h_out[os], OUT_SLOT), "fail to alloc mem", c);
-                const uint64_t o = j * OUT_SLOT, l = (out_bytes - o) < OUT_SLOT ? (out_bytes - o) : OUT_SLOT;
-                CK(mrcz_copy_d2h_async(c, MRCZ_STREAM_DOWNLOAD, s->h_out[os], (char *)D->d_b[b] + o, l), "D2H copy", c);
-                CK(mrcz_event_record(c, MRCZ_STREAM_DOWNLOAD, D->out_ev[os]), "event record", c);
-                if (j + 1 == nsl) CK(mrcz_event_record(c, MRCZ_STREAM_DOWNLOAD, D->down_ev[b]), "event record", c);
-                pthread_mutex_lock(&p->wmu);
-                s->out_dev[os] = di;
-                const int i = p->wq_tail % R_OUT;
-                p->wq[i].slot = os; p->wq[i].off = p->out_off + o; p->wq[i].len = l;
-                p->wq_tail++;
-                pthread_cond_broadcast(&p->wcv);
-                pthread_mutex_unlock(&p->wmu);
-            }
-            oslice += nsl;
-        } else {
-            /* the output cannot seek: slices through the pinned ring, written here in order (the copy of slice j+1 runs while
-             * slice j is written) */
-            uint64_t issued = 0, written = 0;
-            while (written < nsl) {
-                while (issued < nsl && issued < written + R_OUT - 1) {
-                    const int os = (int)((oslice + issued) % R_OUT);
-                    if (!s->h_out[os]) CK(mrcz_host_malloc(c, &s->h_out[os], OUT_SLOT), "fail to alloc mem", c);
-                    const uint64_t o = issued * OUT_SLOT, l = (out_bytes - o) < OUT_SLOT ? (out_bytes - o) : OUT_SLOT;
-                    CK(mrcz_copy_d2h_async(c, MRCZ_STREAM_DOWNLOAD, s->h_out[os], (char *)D->d_b[b] + o, l), "D2H copy", c);
-                    CK(mrcz_event_record(c, MRCZ_STREAM_DOWNLOAD, D->out_ev[os]), "event record", c);
-                    issued++;
-                    if (issued == nsl) CK(mrcz_event_record(c, MRCZ_STREAM_DOWNLOAD, D->down_ev[b]), "event record", c);
-                }
-                const int os = (int)((oslice + written) % R_OUT);
-                const uint64_t o = written * OUT_SLOT, l = (out_bytes - o) < OUT_SLOT ? (out_bytes - o) : OUT_SLOT;
-                double tt = now_sec();
-                CK(mrcz_event_sync(c, D->out_ev[os]), "event sync", c);
-                p->t_d2hwait += now_sec() - tt;
-                tt = now_sec();
-                if (fwrite(s->h_out[os], 1, (size_t)l, p->fout) != l) die("fwrite", NULL); /* workers.c:837-850 / 627,668 */
-                p->t_fwrite += now_sec() - tt;
-                written++;
-            }
-            oslice += nsl;
+        const uint64_t nsl = writes ? (out_bytes + OUT_SLOT - 1) / OUT_SLOT : 0;
+        if (nsl == 0) CK(mrcz_event_record(c, MRCZ_STREAM_DOWNLOAD, D->down_ev[b]), "event record", c);
+        /* every slice: wait for a free ring slot, start its copy, hand it to the sink */
+        for (uint64_t j = 0; j < nsl; j++) {
+            const int os = (int)((oslice + j) % R_OUT);
+            double tt = now_sec();
+            pthread_mutex_lock(&p->wmu);
+            while (p->slot_busy[os]) pthread_cond_wait(&p->wcv, &p->wmu);
+            p->slot_busy[os] = 1;
+            pthread_mutex_unlock(&p->wmu);
+            p->t_sinkwait += now_sec() - tt;
+            if (!s->h_out[os]) CK(mrcz_host_malloc(c, &s->h_out[os], OUT_SLOT), "fail to alloc mem", c);
+            const uint64_t o = j * OUT_SLOT, l = (out_bytes - o) < OUT_SLOT ? (out_bytes - o) : OUT_SLOT;
+            CK(mrcz_copy_d2h_async(c, MRCZ_STREAM_DOWNLOAD, s->h_out[os], (char *)D->d_b[b] + o, l), "D2H copy", c);
+            CK(mrcz_event_record(c, MRCZ_STREAM_DOWNLOAD, D->out_ev[os]), "event record", c);
+            if (j + 1 == nsl) CK(mrcz_event_record(c, MRCZ_STREAM_DOWNLOAD, D->down_ev[b]), "event record", c);
+            pthread_mutex_lock(&p->wmu);
+            s->out_dev[os] = di;
+            const int i = p->wq_tail % R_OUT;
+            p->wq[i].slot = os; p->wq[i].off = p->out_off + o; p->wq[i].len = l;
+            p->wq_tail++;
+            pthread_cond_broadcast(&p->wcv);
+            pthread_mutex_unlock(&p->wmu);
         }
+        oslice += nsl;
         p->out_off += out_bytes;
         pthread_mutex_lock(&p->mu);
         p->n_down = k + 1;
@@ -677,12 +639,12 @@ static void *writer_main(void *arg)
         pthread_mutex_unlock(&p->mu);
         if (bt.last) break;
     }
-    if (par) {
+    if (writes) {
         pthread_mutex_lock(&p->wmu);
         p->wq_done = 1;
         pthread_cond_broadcast(&p->wcv);
         pthread_mutex_unlock(&p->wmu);
-        for (int i = 0; i < nwr; i++) pthread_join(pw[i], NULL);
+        pthread_join(sink, NULL);
         pthread_mutex_destroy(&p->wmu);
         pthread_cond_destroy(&p->wcv);
     }
@@ -693,7 +655,7 @@ static void *writer_main(void *arg)
  * offsets; -1 = not seekable, keep to fwrite */
 static int output_fd(FILE *fout, uint64_t *off)
 {
-    if (isTestThroughput == 1 || getenv("MRCZ_NO_PWRITE")) return -1;
+    if (isTestThroughput == 1) return -1;
     if (fflush(fout) != 0) return -1;
     const int fd = fileno(fout);
     if (fd < 0) return -1;
@@ -711,7 +673,7 @@ static void run_pipeline(pipe_t *p)
     pthread_mutex_init(&p->mu, NULL);
     pthread_cond_init(&p->cv, NULL);
     pthread_t rd, wr;
-    p->crowd = __sync_add_and_fetch(&g_pipes_active, 1); /* (read by the reader and the writer when they size their helper pools) */
+    p->crowd = __sync_add_and_fetch(&g_pipes_active, 1); /* (read by the reader when it sizes its filler pool) */
     if (pthread_create(&rd, NULL, reader_main, p) != 0 || pthread_create(&wr, NULL, writer_main, p) != 0) die("pthread_create", NULL);
     const uint64_t rec_cap = mrcz_records_bound((uint64_t)p->batch_chunks * CHUNK_SIZE) + 64;
     for (uint64_t k = 0;; k++) {
@@ -755,6 +717,32 @@ static void run_pipeline(pipe_t *p)
     pthread_cond_destroy(&p->cv);
 }
 
+/* What run_compress and run_uncompress share: size the batches and the devices for the file, take a session, run the pipeline
+ * described by `p` (direction, input, output, floats), give the session back and leave the output stream after what was
+ * written.  Returns the wall time of the call since `begin`. */
+static double run_file(pipe_t *p, double begin, const char *what)
+{
+    int batch = batch_chunks();
+    const uint64_t file_chunks = (p->total_floats + p->chk - 1) / p->chk;
+    if ((uint64_t)batch > file_chunks) batch = (int)file_chunks; /* a small file does not allocate a whole batch */
+    const uint64_t file_batches = (file_chunks + (uint64_t)batch - 1) / (uint64_t)batch;
+    int nd = thread_ndev(); /* one device per batch of the file at most */
+    if ((uint64_t)nd > file_batches) nd = (int)file_batches;
+    const uint64_t floats = (uint64_t)batch * CHUNK_BYTES, records = mrcz_records_bound((uint64_t)batch * CHUNK_SIZE) + 64;
+    p->s = p->decode ? session_get(records, floats, nd) : session_get(floats, records, nd);
+    if (batch > p->s->d[0].e->batch) batch = p->s->d[0].e->batch;
+    p->nd = nd;
+    p->batch_chunks = batch;
+    p->fd_out = output_fd(p->fout, &p->out_off);
+    p->t_setup = now_sec() - begin;
+    run_pipeline(p);
+    session_put(p->s);
+    if (p->fd_out >= 0) fseeko(p->fout, (off_t)p->out_off, SEEK_SET); /* the stream continues after what pwrite() wrote */
+    const double elapsed = now_sec() - begin;
+    trace_report(p, what, elapsed, p->total_floats * 4);
+    return elapsed;
+}
+
 int run_compress(FILE *fin, ctx_t *ctx, FILE *fout, const int bitsToMask, const char *dataConvertedType)
 {
     /* workers.c:782: strcmp(dataConvertedType, "int") == 0 selects the int mode, anything else is treated as float */
@@ -767,13 +755,6 @@ int run_compress(FILE *fin, ctx_t *ctx, FILE *fout, const int bitsToMask, const 
     const uint64_t fsz = get_file_size(fin);
     const uint64_t file_floats = fsz / 4u;
     if (file_floats == 0) return 0; /* workers.c:757: nothing is written when the first read is empty */
-    int batch = batch_chunks();
-    const uint64_t file_chunks = (file_floats + CHUNK_SIZE - 1) / CHUNK_SIZE;
-    if ((uint64_t)batch > file_chunks) batch = (int)file_chunks; /* a small file does not allocate a whole batch */
-    int nd = thread_ndev(); /* one device per batch of the file at most */
-    if ((uint64_t)nd > (file_chunks + (uint64_t)batch - 1) / (uint64_t)batch) nd = (int)((file_chunks + (uint64_t)batch - 1) / (uint64_t)batch);
-    session_t *ses = session_get((uint64_t)batch * CHUNK_BYTES, mrcz_records_bound((uint64_t)batch * CHUNK_SIZE) + 64, nd);
-    if (batch > ses->d[0].e->batch) batch = ses->d[0].e->batch;
 
     mrczip_header_t hd;
     init_mrczip_header(&hd, 0);
@@ -783,14 +764,8 @@ int run_compress(FILE *fin, ctx_t *ctx, FILE *fout, const int bitsToMask, const 
 
     pipe_t p;
     memset(&p, 0, sizeof(p));
-    p.s = ses; p.nd = nd; p.fin = fin; p.fout = fout; p.decode = 0; p.int_mode = int_mode; p.bits = bitsToMask; p.chk = CHUNK_SIZE; p.total_floats = file_floats; p.batch_chunks = batch;
-    p.fd_out = output_fd(fout, &p.out_off);
-    p.t_setup = now_sec() - begin;
-    run_pipeline(&p);
-    session_put(ses);
-    if (p.fd_out >= 0) fseeko(fout, (off_t)p.out_off, SEEK_SET); /* the stream continues after what pwrite() wrote */
-    const double elapsed = now_sec() - begin;
-    trace_report(&p, "run_compress", elapsed, file_floats * 4);
+    p.fin = fin; p.fout = fout; p.decode = 0; p.int_mode = int_mode; p.bits = bitsToMask; p.chk = CHUNK_SIZE; p.total_floats = file_floats;
+    const double elapsed = run_file(&p, begin, "run_compress");
     ctx->zipTime += elapsed;
     /* workers.c:863-873: the per-plane table, then the sum of the per-plane compressed sizes (each includes its 4-byte header) */
     uint64_t f4[4] = {file_floats, file_floats, file_floats, file_floats};
@@ -814,26 +789,12 @@ int run_uncompress(FILE *fin, ctx_t *ctx, mrczip_header_t *hd, FILE *fout, const
     const double begin = now_sec();
     const uint64_t nfloats = hd->fsz / COMPRESSION_PATH_NUM; /* workers.c:577 */
     if (nfloats == 0) return 0;
-    const uint32_t chk = hd->chk;
-    int batch = batch_chunks();
-    const uint64_t file_chunks = (nfloats + chk - 1) / chk;
-    if ((uint64_t)batch > file_chunks) batch = (int)file_chunks;
-    int nd = thread_ndev();
-    if ((uint64_t)nd > (file_chunks + (uint64_t)batch - 1) / (uint64_t)batch) nd = (int)((file_chunks + (uint64_t)batch - 1) / (uint64_t)batch);
-    session_t *ses = session_get(mrcz_records_bound((uint64_t)batch * CHUNK_SIZE) + 64, (uint64_t)batch * CHUNK_BYTES, nd);
-    if (batch > ses->d[0].e->batch) batch = ses->d[0].e->batch;
 
     pipe_t p;
     memset(&p, 0, sizeof(p));
-    p.s = ses; p.nd = nd; p.fin = fin; p.fout = fout; p.decode = 1; p.int_mode = int_mode; p.chk = chk; p.total_floats = nfloats; p.batch_chunks = batch;
-    p.fd_out = output_fd(fout, &p.out_off);
+    p.fin = fin; p.fout = fout; p.decode = 1; p.int_mode = int_mode; p.chk = hd->chk; p.total_floats = nfloats;
     memcpy(p.ztypes, hd->ztypes, 4);
-    p.t_setup = now_sec() - begin;
-    run_pipeline(&p);
-    session_put(ses);
-    if (p.fd_out >= 0) fseeko(fout, (off_t)p.out_off, SEEK_SET);
-    const double elapsed = now_sec() - begin;
-    trace_report(&p, "run_uncompress", elapsed, nfloats * 4);
+    const double elapsed = run_file(&p, begin, "run_uncompress");
     ctx->unzipTime += elapsed;
     /* workers.c:675-685: the per-plane table; decoded bytes and compressed bytes (plane payloads; chunk headers are not counted) */
     uint64_t f4[4] = {nfloats, nfloats, nfloats, nfloats};

@@ -52,6 +52,56 @@ def test_mrc_tar_on_the_emulator(simbin, oracle, tmp_path, n, bits, tail):
     assert "Decompress Result Info Information" in r.stdout
 
 
+def _run_through_fifos(args, feed=(), drain=(), env=None):
+    """`args` with `cat` feeding each (file, fifo) of `feed` and draining each (fifo, file) of `drain`.  Every process has a
+    timeout: a FIFO whose other end never opens fails the test instead of hanging it."""
+    cats = [subprocess.Popen(["sh", "-c", 'exec cat "$0" > "$1"', str(src), str(fifo)]) for src, fifo in feed]
+    cats += [subprocess.Popen(["sh", "-c", 'exec cat "$0" > "$1"', str(fifo), str(dst)]) for fifo, dst in drain]
+    try:
+        r = _run(args, env)
+        for c in cats:
+            assert c.wait(timeout=60) == 0
+        return r
+    finally:
+        for c in cats:
+            if c.poll() is None:
+                c.kill()
+                c.wait()
+
+
+def _several_batches_and_a_ragged_tail():
+    """three chunks (one per batch with MRCZ_BATCH_CHUNKS=1), the last one partial; zero planes with noisy stretches keep
+    the emulator fast"""
+    n = 2 * util.CHUNK + 12345
+    w = np.zeros(n, np.uint32)
+    w[:256] = util.kat_words(256)
+    for c in range(3):
+        a = c * util.CHUNK + 1000 * (c + 1)
+        w[a: a + 3000] = util.gauss_words(3000, seed=40 + c, header=False)
+    return w
+
+
+def test_fallbacks_for_pipes(simbin, oracle, tmp_path):
+    """Inputs that cannot be mapped are read with fread, outputs that cannot seek are written in order with fwrite: a
+    container written into a FIFO, then decoded from a FIFO into a FIFO, over several batches of several output slices."""
+    w = _several_batches_and_a_ragged_tail()
+    data = w.tobytes() + b"xyz"
+    src, z, back = tmp_path / "in.mrc", tmp_path / "o.zip", tmp_path / "b.mrc"
+    src.write_bytes(data)
+    fin, fout = tmp_path / "in.fifo", tmp_path / "out.fifo"
+    os.mkfifo(fin)
+    os.mkfifo(fout)
+    env = {"MRCZ_BATCH_CHUNKS": "1"}
+    r = _run_through_fifos([simbin["mrc_tar"], "-i", str(src), "-o", str(fout), "-b", "8", "-t", "zip"], drain=[(fout, z)], env=env)
+    assert r.returncode == 0, r.stderr
+    assert "Compression Summary Result Information" in r.stdout                # the tables go to stdout, not into the data
+    assert z.read_bytes() == oracle.compress(data, 8, threads=3)
+    r = _run_through_fifos([simbin["mrc_tar"], "-i", str(fin), "-o", str(fout), "-t", "unzip"], feed=[(z, fin)], drain=[(fout, back)], env=env)
+    assert r.returncode == 0, r.stderr
+    assert "Decompress Result Info Information" in r.stdout
+    assert back.read_bytes() == util.erase_expected(w, 8).tobytes()
+
+
 def test_empty_and_tiny_inputs(simbin, tmp_path):
     src, z = tmp_path / "e.mrc", tmp_path / "e.zip"
     src.write_bytes(b"abc")                                       # fewer than 4 bytes: nothing is written (workers.c:757)
