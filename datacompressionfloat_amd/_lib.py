@@ -11,6 +11,12 @@ class MrczLibraryMissing(ImportError):
     pass
 
 
+class MrczBoxGeom(ctypes.Structure):
+    """mrcz_box_geom_t: a float32 volume of nx x ny x nz words from file word data_word0, boxes of bx x by x bz voxels"""
+    _fields_ = [("data_word0", ctypes.c_uint64), ("nx", ctypes.c_uint32), ("ny", ctypes.c_uint32), ("nz", ctypes.c_uint32),
+                ("bx", ctypes.c_uint32), ("by", ctypes.c_uint32), ("bz", ctypes.c_uint32), ("fill_bits", ctypes.c_uint32)]
+
+
 def load():
     if not os.path.exists(LIB_PATH):
         raise MrczLibraryMissing(
@@ -43,6 +49,13 @@ def load():
     lib.mrcz_records_index.argtypes = [vp, u64, u64, u32, ctypes.POINTER(u64)]
     lib.mrcz_uncompress_range.restype = i32
     lib.mrcz_uncompress_range.argtypes = [vp, vp, u64, u64, u32, u64, u64, u64, vp, i32, ctypes.POINTER(u64)]
+    geom = ctypes.POINTER(MrczBoxGeom)
+    lib.mrcz_box_origins.restype = i32
+    lib.mrcz_box_origins.argtypes = [geom, vp, u32, vp]
+    lib.mrcz_boxes_chunks.restype = i32
+    lib.mrcz_boxes_chunks.argtypes = [geom, vp, u32, u64, u32, vp]
+    lib.mrcz_uncompress_boxes.restype = i32
+    lib.mrcz_uncompress_boxes.argtypes = [vp, vp, u64, u64, u32, u64, u64, geom, vp, u32, vp, i32, ctypes.POINTER(u64)]
     lib.mrcz_generate_kat_words.restype = i32
     lib.mrcz_generate_kat_words.argtypes = [vp, vp, u64, u64]
     lib.mrcz_set_ztypes.restype = i32
@@ -70,4 +83,5 @@ EXPORTS = [
     "mrcz_copy_h2d_async", "mrcz_copy_d2h_async", "mrcz_compress_chunks_async", "mrcz_uncompress_chunks_async",
     "mrcz_set_ztypes", "mrcz_generate_kat_words", "mrcz_err_hist", "mrcz_err_collect", "mrcz_compress_chunks_int8", "mrcz_uncompress_chunks_int8", "mrcz_compress_chunks_int8_async", "mrcz_uncompress_chunks_int8_async",
     "mrcz_record_size", "mrcz_records_index", "mrcz_uncompress_range", "mrcz_uncompress_range_async",
+    "mrcz_box_origins", "mrcz_boxes_chunks", "mrcz_uncompress_boxes",
 ]

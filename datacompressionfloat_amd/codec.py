@@ -10,9 +10,11 @@ import io
 import os
 import struct
 
+import numpy as np
 import torch
 
 from . import _lib
+from ._lib import MrczBoxGeom
 
 CHUNK_FLOATS = 6 * 1048576  # src/include/constant.h:25
 FILE_HEADER_BYTES = 17      # src/core/common.c:137-148
@@ -142,6 +144,31 @@ class MrcZipCodec:
             raise self._err("mrcz_uncompress_range", rc)
         return out[:n], int(consumed.value)
 
+    def uncompress_boxes_device(self, records: torch.Tensor, nfloats_file: int, geom: MrczBoxGeom, origins, first_chunk: int = 0,
+                                nchunks: int = None, out: torch.Tensor = None, int_mode: bool = False, chk: int = CHUNK_FLOATS):
+        """box decode (mrcz_uncompress_boxes): `records` (cuda uint8) = the chunk records of chunks [first_chunk, first_chunk +
+        nchunks) of a file of nfloats_file floats (default: every chunk from first_chunk on); `origins` = (N, 3) box corners
+        x, y, z.  Writes the box voxels that lie in those chunks and every out-of-volume voxel (geom.fill_bits) into `out`, an
+        (N, bz, by, bx) int32 cuda tensor (allocated when None); other voxels are left as they are.  Only the chunks a box
+        touches are decoded.  Returns (out, chunks decoded)."""
+        assert records.is_cuda and records.dtype == torch.uint8 and records.is_contiguous()
+        org = np.ascontiguousarray(np.asarray(origins, dtype=np.int32).reshape(-1, 3))
+        n = len(org)
+        if nchunks is None:
+            nchunks = max((nfloats_file + chk - 1) // chk - first_chunk, 0)
+        shape = (n, geom.bz, geom.by, geom.bx)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=records.device)
+        assert out.is_cuda and out.is_contiguous() and out.element_size() == 4 and out.numel() >= n * geom.bz * geom.by * geom.bx
+        torch.cuda.current_stream(records.device).synchronize()
+        decoded = ctypes.c_uint64()
+        rc = _LIB.mrcz_uncompress_boxes(self._ctx, records.data_ptr(), records.numel(), nfloats_file, chk, first_chunk, nchunks,
+                                        ctypes.byref(geom), org.ctypes.data, n, out.data_ptr(), 1 if int_mode else 0,
+                                        ctypes.byref(decoded))
+        if rc != 0:
+            raise self._err("mrcz_uncompress_boxes", rc)
+        return out, int(decoded.value)
+
     def erase_bits_device(self, words: torch.Tensor, bits: int, first_word_index: int = 0):
         assert words.is_cuda and words.element_size() == 4
         torch.cuda.current_stream(words.device).synchronize()
@@ -229,6 +256,36 @@ class MrcZipCodec:
         out, _ = self.uncompress_range_device(rec, nfl, w0, w1, chk, first_chunk=c_lo, int_mode=(mode == "int"))
         return out
 
+    def _container_header(self, f):
+        """(floats of the file, chunk size) from the 17-byte file header; sets the context's compressor types"""
+        f.seek(0)
+        fsz, chk, typ, ztypes = unpack_file_header(f.read(FILE_HEADER_BYTES))
+        if any(z not in (0, 2, 4) for z in ztypes):
+            raise MrczError("byte stream compressor types must be ZLIB_DEF (0), LZ4_DEF (2) or LZ4HC_DEF (4)")
+        if chk == 0:
+            raise MrczError("chunk size 0 in header (the reference divides by it, src/core/workers.c:589)")
+        rc = _LIB.mrcz_set_ztypes(self._ctx, bytes(bytearray(z & 0xff for z in ztypes)))
+        if rc != 0:
+            raise self._err("mrcz_set_ztypes", rc)
+        return fsz // 4, chk
+
+    def _mrc_volume(self, f):
+        """(data_word0, nx, ny, nz) of the float32 (mode 2) MRC volume in the container open as `f`: the MRC header (nx, ny, nz,
+        mode at bytes 0-15, nsymbt at 92-95) comes from the decoded first 256 words, the data start at byte 1024 + nsymbt (whether
+        the file holds all of it is the caller's check)"""
+        f.seek(0)
+        fsz = unpack_file_header(f.read(FILE_HEADER_BYTES))[0]
+        if fsz // 4 < MRC_HEADER_BYTES // 4:
+            raise MrczError("file shorter than an MRC header")
+        hdr = self._range_device(f, 0, MRC_HEADER_BYTES // 4, "float").cpu().numpy().tobytes()
+        nx, ny, nz, mode = struct.unpack("<4i", hdr[:16])
+        (nsymbt,) = struct.unpack("<i", hdr[92:96])
+        if mode != 2:
+            raise MrczError(f"MRC mode {mode}: only mode 2 (float32) volumes can be read as slabs or boxes")
+        if nx <= 0 or ny <= 0 or nz <= 0 or nsymbt < 0 or nsymbt % 4:
+            raise MrczError(f"implausible MRC header: nx={nx} ny={ny} nz={nz} nsymbt={nsymbt}")
+        return (MRC_HEADER_BYTES + nsymbt) // 4, nx, ny, nz
+
     def _open(self, container_or_path):
         if isinstance(container_or_path, (bytes, bytearray, memoryview)):
             return io.BytesIO(container_or_path)
@@ -247,21 +304,68 @@ class MrcZipCodec:
         with self._open(path) as f:
             f.seek(0)
             fsz = unpack_file_header(f.read(FILE_HEADER_BYTES))[0]
-            if fsz // 4 < MRC_HEADER_BYTES // 4:
-                raise MrczError("file shorter than an MRC header")
-            hdr = self._range_device(f, 0, MRC_HEADER_BYTES // 4, "float").cpu().numpy().tobytes()
-            nx, ny, nz, mode = struct.unpack("<4i", hdr[:16])
-            (nsymbt,) = struct.unpack("<i", hdr[92:96])
-            if mode != 2:
-                raise MrczError(f"MRC mode {mode}: only mode 2 (float32) volumes can be read as slabs")
-            if nx <= 0 or ny <= 0 or nz <= 0 or nsymbt < 0 or nsymbt % 4:
-                raise MrczError(f"implausible MRC header: nx={nx} ny={ny} nz={nz} nsymbt={nsymbt}")
+            d0, nx, ny, nz = self._mrc_volume(f)
             if not 0 <= z0 < z1 <= nz:
                 raise MrczError(f"sections [{z0}, {z1}) outside 0..{nz}")
             sec = nx * ny
-            w0 = (MRC_HEADER_BYTES + nsymbt) // 4 + z0 * sec
+            w0 = d0 + z0 * sec
             w1 = w0 + (z1 - z0) * sec
             if w1 > fsz // 4:
                 raise MrczError("the MRC header describes more data than the file holds")
             out = self._range_device(f, w0, w1, "float")
         return out.view(torch.float32).reshape(z1 - z0, ny, nx)
+
+    def read_mrc_boxes(self, path_or_bytes, centers, size, fill: float = 0.0, mode: str = "float") -> torch.Tensor:
+        """boxes around particle centres of a compressed float32 (mode 2) MRC volume, as an (N, bz, by, bx) float32 cuda tensor.
+        `centers` = (N, 3) x, y, z (integer or float, as pickers write them); `size` = an int or (bx, by, bz).  Box i starts at
+        round(c) - size // 2 per axis (round(v) = floor(v + 0.5)); voxels outside the volume are `fill`.  Reads the file
+        header, the headers of the chunks up to the last one a box touches, and the records of the touched chunks (one read
+        and one decode call per run of them); each touched chunk is decoded once, no other is."""
+        if mode not in ("float", "int"):
+            raise MrczError("mode must be 'float' or 'int' (mrc_tar -s)")
+        bx, by, bz = (int(size),) * 3 if np.ndim(size) == 0 else tuple(int(v) for v in size)
+        if min(bx, by, bz) < 1:
+            raise MrczError(f"box size {(bx, by, bz)}: every side must be at least 1")
+        cen = np.ascontiguousarray(np.asarray(centers, dtype=np.float64).reshape(-1, 3))
+        n = len(cen)
+        with self._open(path_or_bytes) as f:
+            nfl, chk = self._container_header(f)
+            d0, nx, ny, nz = self._mrc_volume(f)
+            if d0 + nx * ny * nz > nfl:
+                raise MrczError("the MRC header describes more data than the file holds")
+            fill_bits = int(np.array([fill], np.float32).view(np.uint32)[0])
+            geom = MrczBoxGeom(d0, nx, ny, nz, bx, by, bz, fill_bits)
+            org = np.zeros((n, 3), np.int32)
+            if _LIB.mrcz_box_origins(ctypes.byref(geom), cen.ctypes.data, n, org.ctypes.data) != 0:
+                raise MrczError("a centre is not finite or its box corner lies outside int32")
+            nch = (nfl + chk - 1) // chk
+            covered = np.zeros(nch, np.uint8)
+            if _LIB.mrcz_boxes_chunks(ctypes.byref(geom), org.ctypes.data, n, nfl, chk, covered.ctypes.data) != 0:
+                raise MrczError("box geometry refused")
+            out = torch.empty((n, bz, by, bx), dtype=torch.int32, device=self.device)
+            idx = np.flatnonzero(covered)
+            # record offsets from the chunk headers, up to the last covered chunk (nothing behind it is read)
+            offs, off, size_ = [], FILE_HEADER_BYTES, ctypes.c_uint64()
+            for c in range(int(idx[-1]) + 1 if len(idx) else 0):
+                offs.append(off)
+                f.seek(off)
+                h = f.read(16)
+                if len(h) < 16 or _LIB.mrcz_record_size(h, min(chk, nfl - c * chk), ctypes.byref(size_)) != 0:
+                    raise MrczError(f"damaged or truncated container: chunk header {c} at byte {off}")
+                off += size_.value
+            offs.append(off)
+            # one read and one decode call per maximal run of covered chunks
+            runs = np.split(idx, np.flatnonzero(np.diff(idx) != 1) + 1) if len(idx) else []
+            for run in runs:
+                c0, c1 = int(run[0]), int(run[-1]) + 1
+                f.seek(offs[c0])
+                body = f.read(offs[c1] - offs[c0])
+                if len(body) != offs[c1] - offs[c0]:
+                    raise MrczError("truncated container: the records of the boxes' chunks end early")
+                rec = torch.frombuffer(bytearray(body), dtype=torch.uint8).to(self.device)
+                self.uncompress_boxes_device(rec, nfl, geom, org, first_chunk=c0, nchunks=c1 - c0, out=out, int_mode=(mode == "int"),
+                                             chk=chk)
+            if not runs:  # every box outside the volume: the fill alone
+                self.uncompress_boxes_device(torch.empty(16, dtype=torch.uint8, device=self.device), nfl, geom, org, nchunks=0,
+                                             out=out, chk=chk)
+        return out.view(torch.float32)

@@ -15,6 +15,7 @@
 
 #include "../../include/mrcz_hip.h"
 
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -89,6 +90,9 @@ struct mrcz_ctx {
     uint32_t lz4_planes;   /* bit j: byte stream j of the containers to decode holds LZ4 blocks (mrcz_set_ztypes) */
     unsigned long long *errhist; /* erroranalysis: 2048 histogram bins + the candidate counter; allocated on first use */
     uint8_t *planes;       /* byte planes of one batch (stream s at s * CHK), both directions; allocated on first use */
+    uint32_t *stage;       /* box decode: the words of one batch (max_chunks x CHK); allocated on first use */
+    uint32_t *boxbuf;      /* box decode: origins and box lists of a call (boxbuf_words words) */
+    uint64_t boxbuf_words;
     /* timing */
     int timing;
     int ntimers;
@@ -223,6 +227,8 @@ extern "C" void mrcz_destroy(mrcz_ctx_t *ctx)
     (void)hipFree(ctx->pairoff); (void)hipFree(ctx->blkbase); (void)hipFree(ctx->result); (void)hipFree(ctx->dstreams); (void)hipFree(ctx->fallback); (void)hipFree(ctx->cands); (void)hipFree(ctx->ncand); (void)hipFree(ctx->candbase); (void)hipFree(ctx->jobord); (void)hipFree(ctx->segs); (void)hipFree(ctx->nseg); (void)hipFree(ctx->segidx); (void)hipFree(ctx->rawlist); (void)hipFree(ctx->scratch); (void)hipFree(ctx->hdrs); (void)hipFree(ctx->njobs);
     (void)hipFree(ctx->dbgphase);
     (void)hipFree(ctx->planes);
+    (void)hipFree(ctx->stage);
+    (void)hipFree(ctx->boxbuf);
     (void)hipFree(ctx->errhist);
     if (ctx->h_result) (void)hipHostFree(ctx->h_result);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -733,6 +739,9 @@ extern "C" int mrcz_uncompress_range_async(mrcz_ctx_t *ctx, const void *d_record
 {
     return uncompress_range_enqueue(ctx, d_records, len, nfloats_file, chk, first_chunk, w0, w1, d_out, h_result3, int_mode);
 }
+
+/* ---- box decode: boxes of a float32 volume out of the records of the chunks they touch ---- */
+#include "mrcz_boxes.hip"
 
 /* ---- events and the three streams of a context (pipelines: include/mrcz_hip.h) ---- */
 struct mrcz_event { hipEvent_t ev; };

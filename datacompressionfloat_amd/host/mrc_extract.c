@@ -1,20 +1,28 @@
 /*
- * mrc_extract.c -- range decode from the command line: part of a container without reading or decoding the rest.
+ * mrc_extract.c -- range and box decode from the command line: part of a container without reading or decoding the rest.
  *
- *   mrc_extract -i vol.mrc.zip -o out.raw (-w first:count | -z z0:z1) [-s float|int] [-g device]
+ *   mrc_extract -i vol.mrc.zip -o out.raw (-w first:count | -z z0:z1 | -B centers.txt -S bx[,by,bz] [-F fill]) [-s float|int]
+ *               [-g device]
  *
  *   -w first:count   words [first, first + count) of the decoded file (4 bytes each)
  *   -z z0:z1         sections [z0, z1) of a float32 (mode 2) MRC volume: nx, ny, nz, mode (bytes 0-15) and nsymbt (bytes 92-95)
  *                    come from the decoded first 256 words, the data start at byte 1024 + nsymbt
+ *   -B centers.txt   boxes of a float32 MRC volume around particle centres, one "x y z" per line (blank lines and lines that
+ *                    start with '#' are skipped); box i starts at round(c) - size / 2 per axis (mrcz_box_origins).  The output
+ *                    is raw float32 in [N][bz][by][bx] order
+ *   -S bx[,by,bz]    box size (one number: a cube)
+ *   -F fill          value of the voxels outside the volume, default 0
  *   -s               decode mode, as mrc_tar -s (the container does not record it)
  *
  * The 17-byte file header and the 16-byte header of every chunk before the window are read with pread; then only the records of
  * the chunks that cover the window, which mrcz_uncompress_range decodes (in one call: the covering records and the window must
- * fit in device memory; the workspace is batched as in every decode).  Not one of the reference's front ends: mrc_tar and
- * mrc_tarx keep the reference's command lines.
+ * fit in device memory; the workspace is batched as in every decode).  -B reads the chunk headers up to the last chunk a box
+ * touches (mrcz_boxes_chunks), then the records of every run of touched chunks, one mrcz_uncompress_boxes call per run.  Not one
+ * of the reference's front ends: mrc_tar and mrc_tarx keep the reference's command lines.
  */
 #include "../../include/mrcz_hip.h"
 
+#include <ctype.h>
 #include <errno.h>
 #include <fcntl.h>
 #include <inttypes.h>
@@ -27,11 +35,16 @@
 
 static void usage(const char *prog)
 {
-    printf("\nUsage:\n\n\t%s -i <container> -o <output file> (-w <first>:<count> | -z <z0>:<z1>) [-s float|int] [-g device]\nwhere:\n", prog);
+    printf("\nUsage:\n\n\t%s -i <container> -o <output file> (-w <first>:<count> | -z <z0>:<z1> | -B <centres> -S <bx>[,<by>,<bz>] [-F <fill>])\n"
+           "\t\t[-s float|int] [-g device]\nwhere:\n", prog);
     printf("\t-i\tcontainer written by mrc_tar -t zip\n\n");
     printf("\t-o\traw output: the decoded words of the window, 4 bytes each\n\n");
     printf("\t-w\twords [first, first + count) of the decoded file\n\n");
     printf("\t-z\tsections [z0, z1) of a float32 (mode 2) MRC volume\n\n");
+    printf("\t-B\tboxes of a float32 (mode 2) MRC volume around the centres in this text file, one \"x y z\" per line;\n"
+           "\t\toutput: raw float32, [N][bz][by][bx]\n\n");
+    printf("\t-S\tbox size with -B: bx, or bx,by,bz\n\n");
+    printf("\t-F\tvalue of box voxels outside the volume, default 0\n\n");
     printf("\t-s\tdata type the container was written with, [float | int], default float\n\n");
     printf("\t-g\tHIP device, default 0\n\n");
 }
@@ -109,28 +122,171 @@ static uint32_t *decode_window(mrcz_ctx_t **pc, int device, const struct contain
     return out;
 }
 
+/* the float32 (mode 2) MRC volume of the container: data_word0, nx, ny, nz into g, from the decoded first 256 words (whether
+ * the file holds all of it is the caller's check) */
+static void mrc_volume(mrcz_ctx_t **pc, int device, const struct container *ct, mrcz_box_geom_t *g)
+{
+    if (ct->nfl < MRC_HEADER_BYTES / 4) die("file shorter than an MRC header", NULL);
+    uint32_t *hdr = decode_window(pc, device, ct, 0, MRC_HEADER_BYTES / 4, 0);
+    int32_t nx = (int32_t)hdr[0], ny = (int32_t)hdr[1], nz = (int32_t)hdr[2], mode = (int32_t)hdr[3], nsymbt = (int32_t)hdr[23];
+    free(hdr);
+    if (mode != 2) die("only float32 (mode 2) MRC volumes can be cut into sections or boxes", NULL);
+    if (nx <= 0 || ny <= 0 || nz <= 0 || nsymbt < 0 || (nsymbt & 3)) die("implausible MRC header (nx, ny, nz, nsymbt)", NULL);
+    g->data_word0 = (MRC_HEADER_BYTES + (uint64_t)nsymbt) / 4;
+    g->nx = (uint32_t)nx; g->ny = (uint32_t)ny; g->nz = (uint32_t)nz;
+}
+
+/* -S bx or bx,by,bz */
+static int parse_size(const char *s, uint32_t sz[3])
+{
+    for (int k = 0; k < 3; k++) {
+        char *e = NULL;
+        if (*s < '0' || *s > '9') return -1;
+        errno = 0;
+        const unsigned long long v = strtoull(s, &e, 10);
+        if (errno || v == 0 || v > 65536u) return -1;
+        sz[k] = (uint32_t)v;
+        if (k == 0 && *e == 0) { sz[1] = sz[2] = sz[0]; return 0; }
+        if (k < 2 ? *e != ',' : *e != 0) return -1;
+        s = e + 1;
+    }
+    return 0;
+}
+
+/* centres file: one "x y z" per line; blank lines and lines starting with '#' skipped */
+static double *read_centres(const char *path, uint32_t *count)
+{
+    FILE *f = fopen(path, "r");
+    if (!f) die("cannot open the centres file (-B)", NULL);
+    size_t cap = 1024, n = 0, lineno = 0;
+    double *c = (double *)malloc(cap * 3 * sizeof(double));
+    char line[4096];
+    if (!c) die("out of memory", NULL);
+    while (fgets(line, sizeof line, f)) {
+        lineno++;
+        const size_t ll = strlen(line);
+        if (ll == sizeof line - 1 && line[ll - 1] != '\n') die("a line of the centres file is too long", NULL);
+        char *p = line;
+        while (isspace((unsigned char)*p)) p++;
+        if (*p == 0 || *p == '#') continue;
+        if (n == cap) {
+            cap *= 2;
+            c = (double *)realloc(c, cap * 3 * sizeof(double));
+            if (!c) die("out of memory", NULL);
+        }
+        for (int k = 0; k < 3; k++) {
+            char *e = NULL;
+            errno = 0;
+            c[3 * n + k] = strtod(p, &e);
+            if (e == p || errno || (*e && !isspace((unsigned char)*e))) {
+                fprintf(stderr, "centres file line %zu: ", lineno);
+                die("want three numbers \"x y z\" per line", NULL);
+            }
+            p = e;
+        }
+        while (isspace((unsigned char)*p)) p++;
+        if (*p) {
+            fprintf(stderr, "centres file line %zu: ", lineno);
+            die("want three numbers \"x y z\" per line", NULL);
+        }
+        if (++n > 0x7fffffffu) die("too many centres", NULL);
+    }
+    if (ferror(f)) die("read error in the centres file", NULL);
+    fclose(f);
+    *count = (uint32_t)n;
+    return c;
+}
+
+/* boxes of g around the n centres, decoded on the device, into a malloc'ed host buffer of n * bz * by * bx words */
+static uint32_t *decode_boxes(mrcz_ctx_t *c, const struct container *ct, mrcz_box_geom_t *g, const double *centres, uint32_t n, int int_mode)
+{
+    const uint64_t chk = ct->chk, nch = (ct->nfl + chk - 1) / chk, words = (uint64_t)n * g->bz * g->by * g->bx;
+    int32_t *org = (int32_t *)malloc(12u * (size_t)n + 12u);
+    uint8_t *covered = (uint8_t *)malloc((size_t)nch);
+    uint64_t *offs = (uint64_t *)malloc(8u * (size_t)(nch + 1));
+    uint32_t *out = (uint32_t *)malloc(4u * (size_t)words + 4u);
+    if (!org || !covered || !offs || !out) die("out of memory", NULL);
+    if (mrcz_box_origins(g, centres, n, org) != MRCZ_OK) die("a centre is not a finite number or its box lies outside int32", NULL);
+    if (mrcz_boxes_chunks(g, org, n, ct->nfl, ct->chk, covered) != MRCZ_OK) die("box geometry", NULL);
+    uint64_t last = 0; /* chunks [0, last) hold every covered one */
+    for (uint64_t k = 0; k < nch; k++)
+        if (covered[k]) last = k + 1;
+    uint64_t off = MRCZ_FILE_HEADER_BYTES, biggest = 0;
+    for (uint64_t k = 0; k < last; k++) { /* 16 bytes per chunk up to the last covered one, nothing behind it */
+        uint8_t h[16];
+        uint64_t bytes = 0;
+        const uint64_t left = ct->nfl - k * chk;
+        offs[k] = off;
+        pread_all(ct->fd, h, 16, off, "truncated container (chunk header)");
+        if (mrcz_record_size(h, (uint32_t)(left < chk ? left : chk), &bytes) != MRCZ_OK) die("damaged chunk header", NULL);
+        off += bytes;
+    }
+    offs[last] = off;
+    for (uint64_t k = 0; k < last;) { /* the largest run of covered chunks sizes the record buffers */
+        uint64_t e = k;
+        while (e < last && covered[e]) e++;
+        if (e > k && offs[e] - offs[k] > biggest) biggest = offs[e] - offs[k];
+        k = e > k ? e : k + 1;
+    }
+    void *h_rec = NULL, *d_rec = NULL, *d_out = NULL;
+    if (mrcz_dev_malloc(c, &d_out, words ? 4 * words : 16)) die("out of device memory", c);
+    if (biggest && (mrcz_host_malloc(c, &h_rec, biggest) || mrcz_dev_malloc(c, &d_rec, biggest))) die("out of memory", c);
+    uint64_t runs = 0;
+    for (uint64_t k = 0; k < last;) { /* one read and one decode call per run of covered chunks */
+        if (!covered[k]) { k++; continue; }
+        uint64_t e = k, dec = 0;
+        while (e < last && covered[e]) e++;
+        const uint64_t len = offs[e] - offs[k];
+        pread_all(ct->fd, h_rec, len, offs[k], "truncated container (payload)");
+        if (mrcz_copy_h2d(c, d_rec, h_rec, len) != MRCZ_OK) die("copy to the device", c);
+        if (mrcz_uncompress_boxes(c, d_rec, len, ct->nfl, ct->chk, k, e - k, g, org, n, d_out, int_mode, &dec) != MRCZ_OK) die("box decode", c);
+        runs++;
+        k = e;
+    }
+    if (!runs && mrcz_uncompress_boxes(c, NULL, 0, ct->nfl, ct->chk, 0, 0, g, org, n, d_out, int_mode, NULL) != MRCZ_OK) die("box decode", c);
+    if (words && mrcz_copy_d2h(c, out, d_out, 4 * words) != MRCZ_OK) die("copy from the device", c);
+    mrcz_dev_free(c, d_out);
+    if (biggest) { mrcz_dev_free(c, d_rec); mrcz_host_free(c, h_rec); }
+    free(org); free(covered); free(offs);
+    return out;
+}
+
 int main(int argc, char *argv[])
 {
-    const char *in = NULL, *outp = NULL, *wspec = NULL, *zspec = NULL, *dtype = "float";
+    const char *in = NULL, *outp = NULL, *wspec = NULL, *zspec = NULL, *bspec = NULL, *sspec = NULL, *fspec = NULL, *dtype = "float";
     int opt, device = 0;
     if (argc < 2) { usage(argv[0]); return 255; }
-    while ((opt = getopt(argc, argv, "hi:o:w:z:s:g:")) != -1) {
+    while ((opt = getopt(argc, argv, "hi:o:w:z:B:S:F:s:g:")) != -1) {
         switch (opt) {
         case 'i': in = optarg; break;
         case 'o': outp = optarg; break;
         case 'w': wspec = optarg; break;
         case 'z': zspec = optarg; break;
+        case 'B': bspec = optarg; break;
+        case 'S': sspec = optarg; break;
+        case 'F': fspec = optarg; break;
         case 's': dtype = optarg; break;
         case 'g': device = atoi(optarg); break;
         case 'h': usage(argv[0]); return 0;
         default: usage(argv[0]); return 255;
         }
     }
-    if (!in || !outp || !!wspec == !!zspec) { usage(argv[0]); die("need -i, -o and one of -w, -z", NULL); }
+    if (!in || !outp || !!wspec + !!zspec + !!bspec != 1) { usage(argv[0]); die("need -i, -o and one of -w, -z, -B", NULL); }
+    if (!bspec && (sspec || fspec)) die("-S and -F go with -B", NULL);
     const int int_mode = strcmp(dtype, "int") == 0;
     if (!int_mode && strcmp(dtype, "float") != 0) die("-s must be float or int", NULL);
     uint64_t a = 0, b = 0;
-    if (parse_pair(wspec ? wspec : zspec, &a, &b)) die(wspec ? "-w wants first:count" : "-z wants z0:z1", NULL);
+    uint32_t bsize[3] = {0, 0, 0};
+    float fill = 0.f;
+    if (bspec) {
+        if (!sspec) die("-B needs a box size (-S bx or -S bx,by,bz)", NULL);
+        if (parse_size(sspec, bsize)) die("-S wants bx or bx,by,bz (each 1 .. 65536)", NULL);
+        if (fspec) {
+            char *e = NULL;
+            fill = strtof(fspec, &e);
+            if (e == fspec || *e) die("-F wants a number", NULL);
+        }
+    } else if (parse_pair(wspec ? wspec : zspec, &a, &b)) die(wspec ? "-w wants first:count" : "-z wants z0:z1", NULL);
 
     struct container ct;
     ct.fd = open(in, O_RDONLY);
@@ -147,21 +303,40 @@ int main(int argc, char *argv[])
         if (ct.ztypes[j] != 0 && ct.ztypes[j] != 2 && ct.ztypes[j] != 4) die("unknown byte stream compressor type in the file header", NULL);
 
     mrcz_ctx_t *c = NULL;
+    if (bspec) {
+        uint32_t n = 0;
+        double *centres = read_centres(bspec, &n);
+        const uint64_t nch = (ct.nfl + ct.chk - 1) / ct.chk;
+        if (ct.nfl == 0) die("empty container", NULL);
+        if (mrcz_create(&c, device, (uint32_t)(nch < 16 ? nch : 16)) != MRCZ_OK) die("no usable HIP device (the codec has no CPU path)", NULL);
+        mrcz_box_geom_t g;
+        mrc_volume(&c, device, &ct, &g);
+        if (g.data_word0 + (uint64_t)g.nx * g.ny * g.nz > ct.nfl) die("the MRC header describes more data than the file holds", NULL);
+        g.bx = bsize[0]; g.by = bsize[1]; g.bz = bsize[2];
+        memcpy(&g.fill_bits, &fill, 4);
+        uint32_t *out = decode_boxes(c, &ct, &g, centres, n, int_mode);
+        const size_t words = (size_t)n * g.bz * g.by * g.bx;
+        FILE *fo = fopen(outp, "wb");
+        if (!fo) die("cannot open the output file", NULL);
+        if (fwrite(out, 4, words, fo) != words || fclose(fo) != 0) die("write", NULL);
+        printf("%u boxes of %u x %u x %u written to %s\n", n, g.bx, g.by, g.bz, outp);
+        free(out);
+        free(centres);
+        close(ct.fd);
+        fflush(stdout);
+        _exit(0);
+    }
     uint64_t w0, w1;
     if (wspec) {
         w0 = a;
         w1 = a + b;
         if (b == 0 || w1 < w0 || w1 > ct.nfl) die("-w window empty or past the end of the file", NULL);
     } else {
-        if (ct.nfl < MRC_HEADER_BYTES / 4) die("file shorter than an MRC header", NULL);
-        uint32_t *hdr = decode_window(&c, device, &ct, 0, MRC_HEADER_BYTES / 4, 0);
-        int32_t nx = (int32_t)hdr[0], ny = (int32_t)hdr[1], nz = (int32_t)hdr[2], mode = (int32_t)hdr[3], nsymbt = (int32_t)hdr[23];
-        free(hdr);
-        if (mode != 2) die("only float32 (mode 2) MRC volumes can be cut into sections", NULL);
-        if (nx <= 0 || ny <= 0 || nz <= 0 || nsymbt < 0 || (nsymbt & 3)) die("implausible MRC header (nx, ny, nz, nsymbt)", NULL);
-        if (a >= b || b > (uint64_t)nz) die("-z sections outside the volume", NULL);
-        const uint64_t sec = (uint64_t)nx * (uint64_t)ny;
-        w0 = (MRC_HEADER_BYTES + (uint64_t)nsymbt) / 4 + a * sec;
+        mrcz_box_geom_t g;
+        mrc_volume(&c, device, &ct, &g);
+        if (a >= b || b > (uint64_t)g.nz) die("-z sections outside the volume", NULL);
+        const uint64_t sec = (uint64_t)g.nx * (uint64_t)g.ny;
+        w0 = g.data_word0 + a * sec;
         w1 = w0 + (b - a) * sec;
         if (w1 > ct.nfl) die("the MRC header describes more data than the file holds", NULL);
     }

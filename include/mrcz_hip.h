@@ -174,6 +174,40 @@ int mrcz_uncompress_range(mrcz_ctx_t *ctx, const void *d_records, uint64_t len, 
 int mrcz_uncompress_range_async(mrcz_ctx_t *ctx, const void *d_records, uint64_t len, uint64_t nfloats_file, uint32_t chk,
                                 uint64_t first_chunk, uint64_t w0, uint64_t w1, void *d_out, int int_mode, uint64_t *h_result3);
 
+/*
+ * Box decode: a batch of equal-sized boxes (particle sub-volumes) of a float32 volume, decoding only the chunks the boxes touch.
+ * The volume is nx x ny x nz words starting at file word data_word0 (an MRC file: 256 + nsymbt / 4); voxel (x, y, z) is file
+ * word data_word0 + (z * ny + y) * nx + x.  Box i has origin (corner) (x0, y0, z0) = origins[3 i .. 3 i + 2]; output word
+ * [i][k][j][l] (nboxes x bz x by x bx words) is voxel (x0 + l, y0 + j, z0 + k), or fill_bits where that voxel lies outside the
+ * volume.  Boxes may overlap each other and may lie partly or wholly outside the volume.
+ *   mrcz_box_origins      (host) origins of boxes centred on centres[3 i .. 3 i + 2] (x, y, z, as particle pickers write
+ *                         them): round(c) - size / 2 per axis, round(v) = floor(v + 0.5).  MRCZ_EINVAL for a centre that is
+ *                         not finite or an origin outside int32
+ *   mrcz_boxes_chunks     (host) covered[c] = 1 iff an in-volume voxel of some box lies in chunk c, else 0, for every chunk
+ *                         c < ceil(nfloats_file / chk)
+ *   mrcz_uncompress_boxes d_records/len = the records of chunks [first_chunk, first_chunk + nchunks) of the file (d_records
+ *                         may be NULL when nchunks = 0).  Writes every box voxel that lies in those chunks, and every
+ *                         out-of-volume voxel, into d_out (16-byte aligned); leaves every other voxel untouched, so one call
+ *                         per run of covered chunks gives what one call over the whole span gives.  Covered chunks are
+ *                         decoded once, the others only walked (16-byte header).  int_mode and mrcz_set_ztypes apply as in
+ *                         range decode.  MRCZ_EINVAL: a zero size, a volume that does not fit in nfloats_file, a NULL
+ *                         pointer, first_chunk + nchunks past the file; MRCZ_EFORMAT: records that end before the last
+ *                         chunk's record does (never read past len).  chunks_decoded (optional) = covered chunks decoded.
+ *                         nboxes = 0 does nothing.  Synchronous.
+ */
+typedef struct mrcz_box_geom {
+    uint64_t data_word0;  /* file word of voxel (0, 0, 0) */
+    uint32_t nx, ny, nz;  /* volume, each >= 1 */
+    uint32_t bx, by, bz;  /* box size, each >= 1 */
+    uint32_t fill_bits;   /* word written for out-of-volume voxels */
+} mrcz_box_geom_t;
+int mrcz_box_origins(const mrcz_box_geom_t *g, const double *h_centers, uint32_t nboxes, int32_t *h_origins);
+int mrcz_boxes_chunks(const mrcz_box_geom_t *g, const int32_t *h_origins, uint32_t nboxes, uint64_t nfloats_file, uint32_t chk,
+                      uint8_t *covered);
+int mrcz_uncompress_boxes(mrcz_ctx_t *ctx, const void *d_records, uint64_t len, uint64_t nfloats_file, uint32_t chk,
+                          uint64_t first_chunk, uint64_t nchunks, const mrcz_box_geom_t *g, const int32_t *h_origins,
+                          uint32_t nboxes, void *d_out, int int_mode, uint64_t *chunks_decoded);
+
 /* apply_mask alone on device (the erasebytes restatement used by the GPU-side verification tools,
  * src/tool/erasebytes.c:109-134): words [256, nwords) of a file &= mask(bits).  In place. */
 int mrcz_erase_bits(mrcz_ctx_t *ctx, void *d_words, uint64_t nwords, uint64_t first_word_index, int bits);
