@@ -80,6 +80,12 @@ class MrcZipCodec:
         """streams of the last uncompress call that needed the sequential general-distance decoder"""
         return int(_LIB.mrcz_debug_fallbacks(self._ctx))
 
+    def last_chain_fallbacks(self) -> int:
+        """streams of the last uncompress call whose block chain did not close in parallel and that were decoded block after
+        block instead (static blocks, headers outside the candidate pattern, more blocks or segments than the per-stream
+        limits; includes the streams counted by last_fallbacks)"""
+        return int(_LIB.mrcz_debug_chain_fallbacks(self._ctx))
+
     @staticmethod
     def records_bound(nfloats: int) -> int:
         return int(_LIB.mrcz_records_bound(nfloats))

@@ -102,8 +102,18 @@ struct mrcz_ctx {
     /* inspection */
     uint32_t last_streams;
     uint32_t last_nlanes, last_lc0[MAX_LANES], last_row0[MAX_LANES]; /* lanes of the last compressed batch: first chunk, first workspace row */
-    uint64_t last_fallbacks;
+    uint64_t last_fallbacks;       /* result words 2 and 3 of the last synchronous uncompress call, latched when it returns */
+    uint64_t last_chain_fallbacks;
 };
+
+/* Result words an uncompress call copies back in stream order: the three of the async ABI (h_result3), and into the context's own
+ * mirror a fourth as well (streams k_inflate_par took over), which the synchronous calls latch together with the third. */
+static size_t result_words(const mrcz_ctx *ctx, const uint64_t *h_res) { return h_res == ctx->h_result ? 4u : 3u; }
+static void latch_fallbacks(mrcz_ctx *ctx)
+{
+    ctx->last_fallbacks = ctx->h_result[2];
+    ctx->last_chain_fallbacks = ctx->h_result[3];
+}
 
 static int fail(mrcz_ctx *c, int code, const char *what, hipError_t e)
 {
@@ -599,7 +609,7 @@ static int uncompress_enqueue(mrcz_ctx_t *ctx, const void *d_records, uint64_t l
         LAUNCH("k_merge_segments", k_merge_segments<false>, dim3(512, nb), dim3(256), rec, ctx->scratch + 16, ctx->planes, ctx->segs, ctx->nseg, ctx->segidx, bfl,
                chk, out + c0 * chk, len, (uint64_t)4 * ctx->row_chunks * CHK, int_mode ? 1u : 0u, (first_chunk + c0) * (uint64_t)chk, (int64_t)0, (uint64_t)0);
     }
-    HIPCHK(hipMemcpyAsync(h_res, ctx->result, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream), "copy result");
+    HIPCHK(hipMemcpyAsync(h_res, ctx->result, result_words(ctx, h_res) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream), "copy result");
     return MRCZ_OK;
 }
 
@@ -615,7 +625,7 @@ extern "C" int mrcz_uncompress_chunks(mrcz_ctx_t *ctx, const void *d_records, ui
     HIPCHK(hipStreamSynchronize(ctx->stream), "stream sync (uncompress)");
     if (ctx->trace) fprintf(stderr, "[mrcz trace] uncompress %llu floats: enqueue %.1f us, wait %.1f us\n", (unsigned long long)nfloats, 1e6 * (t1 - t0), 1e6 * (wall_now() - t1));
     if (consumed) *consumed = ctx->h_result[0];
-    ctx->last_fallbacks = ctx->h_result[2];
+    latch_fallbacks(ctx);
     if (ctx->h_result[1]) return fail(ctx, MRCZ_EFORMAT, "malformed chunk records or deflate stream", hipSuccess);
     return MRCZ_OK;
 }
@@ -637,7 +647,7 @@ extern "C" int mrcz_uncompress_chunks_int8(mrcz_ctx_t *ctx, const void *d_record
     if (int rc = uncompress_enqueue(ctx, d_records, len, nfloats, chk, d_out, ctx->h_result, 1, first_chunk)) return rc;
     HIPCHK(hipStreamSynchronize(ctx->stream), "stream sync (uncompress)");
     if (consumed) *consumed = ctx->h_result[0];
-    ctx->last_fallbacks = ctx->h_result[2];
+    latch_fallbacks(ctx);
     if (ctx->h_result[1]) return fail(ctx, MRCZ_EFORMAT, "malformed chunk records or deflate stream", hipSuccess);
     return MRCZ_OK;
 }
@@ -717,7 +727,7 @@ static int uncompress_range_enqueue(mrcz_ctx_t *ctx, const void *d_records, uint
         LAUNCH("k_merge_window", k_merge_segments<true>, dim3(gx, nb), dim3(256), rec, ctx->scratch + 16, ctx->planes, ctx->segs, ctx->nseg, ctx->segidx, bfl,
                chk, out, len, (uint64_t)4 * ctx->row_chunks * CHK, int_mode ? 1u : 0u, bbase, wlo, whi);
     }
-    HIPCHK(hipMemcpyAsync(h_res, ctx->result, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream), "copy result");
+    HIPCHK(hipMemcpyAsync(h_res, ctx->result, result_words(ctx, h_res) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream), "copy result");
     return MRCZ_OK;
 }
 
@@ -729,7 +739,7 @@ extern "C" int mrcz_uncompress_range(mrcz_ctx_t *ctx, const void *d_records, uin
     if (int rc = uncompress_range_enqueue(ctx, d_records, len, nfloats_file, chk, first_chunk, w0, w1, d_out, ctx->h_result, int_mode)) return rc;
     HIPCHK(hipStreamSynchronize(ctx->stream), "stream sync (uncompress range)");
     if (consumed) *consumed = ctx->h_result[0];
-    ctx->last_fallbacks = ctx->h_result[2];
+    latch_fallbacks(ctx);
     if (ctx->h_result[1]) return fail(ctx, MRCZ_EFORMAT, "malformed chunk records or deflate stream", hipSuccess);
     return MRCZ_OK;
 }
@@ -972,15 +982,9 @@ extern "C" int mrcz_debug_candidates(mrcz_ctx_t *ctx, uint64_t out[2])
 }
 
 extern "C" int64_t mrcz_debug_fallbacks(const mrcz_ctx_t *ctx) { return ctx ? (int64_t)ctx->last_fallbacks : -1; }
-/* streams of the last uncompress call whose block chain the parallel path could not close (too many candidates or segments, no
+/* streams of the last synchronous uncompress call whose block chain the parallel path could not close (too many candidates or segments, no
  * scratch room, static blocks ...) and that k_inflate_par decoded block after block instead */
-extern "C" int64_t mrcz_debug_chain_fallbacks(mrcz_ctx_t *ctx)
-{
-    if (!ctx) return -1;
-    uint64_t v = 0;
-    if (hipSetDevice(ctx->device) != hipSuccess || hipMemcpy(&v, ctx->result + 3, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return (int64_t)v;
-}
+extern "C" int64_t mrcz_debug_chain_fallbacks(mrcz_ctx_t *ctx) { return ctx ? (int64_t)ctx->last_chain_fallbacks : -1; }
 
 extern "C" int mrcz_debug_blocks(mrcz_ctx_t *ctx, uint32_t stream, mrcz_block_info_t *blocks, uint32_t max_blocks)
 {

@@ -221,7 +221,7 @@ static int uncompress_boxes_enqueue(mrcz_ctx *ctx, const uint8_t *rec, uint64_t 
     }
     /* the chunks behind the last run are walked too: records that end before the span does are refused */
     if (int rc = walk_chunks(ctx, rec, len, nfloats_file, chk, c, first_chunk + nchunks)) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->h_result, ctx->result, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream), "copy result");
+    HIPCHK(hipMemcpyAsync(ctx->h_result, ctx->result, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream), "copy result");
     return MRCZ_OK;
 }
 
@@ -300,7 +300,7 @@ extern "C" int mrcz_uncompress_boxes(mrcz_ctx_t *ctx, const void *d_records, uin
     free(h);
     free(runs);
     if (rc) return rc;
-    ctx->last_fallbacks = ctx->h_result[2];
+    latch_fallbacks(ctx);
     if (ctx->h_result[1]) return fail(ctx, MRCZ_EFORMAT, "malformed chunk records or deflate stream", hipSuccess);
     if (chunks_decoded) *chunks_decoded = decoded;
     return MRCZ_OK;

@@ -30,8 +30,11 @@
  *       byte a distance-1 match replicates and the lane that ended the block;
  *   P4  lanes walk once more and write plane bytes (packed dword stores, wide stores for long runs).
  * Streams written by this codec (and by zlib Z_RLE) only contain distance-1 matches and tokens of at most 15+5+1
- * bits; a stream with other distances or tokens longer than 24 bits is handed to the sequential decoder in
- * mrcz_inflate.hip.
+ * bits; a stream with other distances, tokens longer than MAXTOK (24) bits or distance codes longer than DBITS (10)
+ * bits is handed to the sequential decoder in mrcz_inflate.hip.  Only the block at payload bit 0 and blocks of the
+ * candidate pattern (BFINAL 0, BTYPE 2, HDIST field 1) are decoded speculatively; static blocks, dynamic blocks with
+ * other headers, a final block behind the first one and stored blocks with BFINAL 1 leave the chain open, and the
+ * stream is decoded by k_inflate_par.
  */
 #include "mrcz_common.h"
 #include "mrcz_tile.h"
@@ -1686,6 +1689,10 @@ __global__ __launch_bounds__(64) void k_scan_candidates(const uint8_t *__restric
         const uint32_t pending = nq < (uint32_t)SCAN_QCAP ? nq : (uint32_t)SCAN_QCAP;
         const uint64_t step_bit0 = (w_first + (uint64_t)k * 256u) << 5;
         for (uint32_t qr = 0; qr < pending; qr += 64u) {
+            /* every lane's survivors of the previous round are in sn before any lane reads it: flush_survivors reserves
+             * min(sn, SURV_CAP) raw-list slots on lane 0 and each lane fills its share by the sn IT read, so lanes that
+             * disagree leave reserved slots unwritten (k_validate_wave then reads a stream number from garbage) */
+            __builtin_amdgcn_wave_barrier();
             if (qr && sn > SURV_CAP - 64u) flush_survivors(); /* wave-uniform (sn is read by the whole wave at once) */
             const uint32_t qi0 = qr + lane;
             if (qi0 >= pending) continue;

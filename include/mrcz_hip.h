@@ -252,11 +252,13 @@ typedef struct {
 } mrcz_block_info_t;
 int mrcz_debug_blocks(mrcz_ctx_t *ctx, uint32_t stream, mrcz_block_info_t *blocks, uint32_t max_blocks);
 
-/* Inspection (tests): number of streams of the last mrcz_uncompress_chunks call that the parallel
- * decoder handed to the sequential general-distance decoder (0 for streams this codec or zlib
- * Z_RLE wrote). */
+/* Inspection (tests): number of streams of the last synchronous uncompress call (chunks, range or
+ * boxes) that the parallel decoder handed to the sequential general-distance decoder (0 for streams
+ * this codec or zlib Z_RLE wrote), and of streams decoded block after block because their block
+ * chain did not close in parallel (a superset of the former).  Both are latched when the call
+ * returns: a later compress call does not change them. */
 int64_t mrcz_debug_fallbacks(const mrcz_ctx_t *ctx);
-int64_t mrcz_debug_chain_fallbacks(mrcz_ctx_t *ctx); /* streams of the last uncompress call decoded block after block (chain not closed in parallel) */
+int64_t mrcz_debug_chain_fallbacks(mrcz_ctx_t *ctx);
 
 /* Inspection (profiling): enable/disable the in-kernel phase counters of the parallel inflate and
  * (if out != NULL) read the 20 counters of `stream` from the last call (shader clocks of thread 0):

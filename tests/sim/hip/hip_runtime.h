@@ -122,7 +122,16 @@ static inline void __threadfence() {}
 static inline void __threadfence_block() {}
 
 /* ---- host runtime subset ---- */
-static inline hipError_t hipMalloc(void **p, size_t n) { *p = malloc(n ? n : 1); return *p ? hipSuccess : 2; }
+/* -DSIM_POISON_DEVICE=<byte>: fresh device memory holds that byte instead of whatever malloc returns, as a GPU's does not
+ * hold zeros either (a kernel that reads memory nobody wrote then goes wrong the same way on every run) */
+static inline hipError_t hipMalloc(void **p, size_t n)
+{
+    *p = malloc(n ? n : 1);
+#ifdef SIM_POISON_DEVICE
+    if (*p) memset(*p, SIM_POISON_DEVICE, n);
+#endif
+    return *p ? hipSuccess : 2;
+}
 template <typename T> static inline hipError_t hipMalloc(T **p, size_t n) { return hipMalloc((void **)p, n); }
 static inline hipError_t hipFree(void *p) { free(p); return hipSuccess; }
 #define hipHostMallocPortable 0x1u

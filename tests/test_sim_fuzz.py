@@ -75,27 +75,38 @@ print("FUZZ-OK", decoded, rejected)
 '''
 
 
-@pytest.fixture(scope="module")
-def asan_sim(tmp_path_factory):
-    """The product's HIP sources compiled against the emulator with AddressSanitizer, ONE build for both tests below.  The
-    decoder's per-stream limits are lowered (-DMRCZ_MAXCAND=48 -DMRCZ_MAXSEG=16) so that inputs small enough for the emulator
-    run into them; the fuzz containers (two or three blocks per stream) stay below them."""
+def _asan_build(tmp_path_factory, *defines):
+    """The product's HIP sources compiled against the emulator with AddressSanitizer; fresh device memory is poisoned
+    (-DSIM_POISON_DEVICE) so that a kernel reading memory nobody wrote fails on every run, not by chance."""
     asan_rt = subprocess.run(["gcc", "-print-file-name=libasan.so"], stdout=subprocess.PIPE, text=True).stdout.strip()
     if not os.path.isabs(asan_rt) or not os.path.exists(asan_rt):
         pytest.skip("no AddressSanitizer runtime in this image")
     so = tmp_path_factory.mktemp("asan") / "libmrcz_sim_asan.so"
     csrc = os.path.join(util.ROOT, "datacompressionfloat_amd", "csrc")
     subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-I" + util.SIM_DIR, "-I" + csrc, "-Wno-attributes",
-                           "-Wno-unknown-pragmas", "-fsanitize=address", "-fno-omit-frame-pointer", "-DMRCZ_MAXCAND=48", "-DMRCZ_MAXSEG=16", "-shared", "-o", str(so),
-                           os.path.join(csrc, "mrcz_api.hip"), os.path.join(util.SIM_DIR, "sim_runtime.cpp")])
+                           "-Wno-unknown-pragmas", "-fsanitize=address", "-fno-omit-frame-pointer", "-DSIM_POISON_DEVICE=0xa5", *defines,
+                           "-shared", "-o", str(so), os.path.join(csrc, "mrcz_api.hip"), os.path.join(util.SIM_DIR, "sim_runtime.cpp")])
     return str(so), asan_rt
+
+
+@pytest.fixture(scope="module")
+def asan_sim(tmp_path_factory):
+    """the shipped per-stream limits (MRCZ_MAXCAND, MRCZ_MAXSEG): the arrays and index arithmetic they size are checked as shipped"""
+    return _asan_build(tmp_path_factory)
+
+
+@pytest.fixture(scope="module")
+def asan_sim_lowered(tmp_path_factory):
+    """the decoder's per-stream limits lowered (-DMRCZ_MAXCAND=48 -DMRCZ_MAXSEG=16) so that inputs small enough for the
+    emulator run into them"""
+    return _asan_build(tmp_path_factory, "-DMRCZ_MAXCAND=48", "-DMRCZ_MAXSEG=16")
 
 
 def test_corrupted_containers_never_touch_foreign_memory(tmp_path, asan_sim):
     so, asan_rt = asan_sim
     script = tmp_path / "fuzz.py"
     script.write_text(SCRIPT)
-    env = dict(os.environ, REPO=util.ROOT, SIM_ASAN=so, CASES="12", LD_PRELOAD=asan_rt,
+    env = dict(os.environ, REPO=util.ROOT, SIM_ASAN=so, CASES="24", LD_PRELOAD=asan_rt,
                ASAN_OPTIONS="detect_leaks=0:detect_stack_use_after_return=0:abort_on_error=1")
     r = subprocess.run([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
     assert r.returncode == 0 and "FUZZ-OK" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
@@ -150,11 +161,11 @@ print("CLIFF-OK", what, sim.chain_fallbacks, sim.fallbacks)
 '''
 
 
-def test_decoder_cliffs_fall_back_with_the_right_bytes(tmp_path, asan_sim):
+def test_decoder_cliffs_fall_back_with_the_right_bytes(tmp_path, asan_sim_lowered):
     """Streams that exceed what the block-parallel decoder keeps per stream -- candidates (MAXCAND), segments (MAXSEG), scratch
     room -- must come out of k_inflate_par / k_inflate byte for byte.  The sanitizer build lowers the limits (-DMRCZ_MAXCAND=48
     -DMRCZ_MAXSEG=16, MRCZ_SCRATCH_BYTES) so that inputs small enough for the emulator run into them."""
-    so, asan_rt = asan_sim
+    so, asan_rt = asan_sim_lowered
     script = tmp_path / "cliff.py"
     script.write_text(CLIFF_SCRIPT)
     for what in ("maxcand", "maxseg", "scratch"):
@@ -165,3 +176,33 @@ def test_decoder_cliffs_fall_back_with_the_right_bytes(tmp_path, asan_sim):
         r = subprocess.run([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
         assert r.returncode == 0 and "CLIFF-OK" in r.stdout, (what, r.stdout[-2000:], r.stderr[-4000:])
         assert "ERROR: AddressSanitizer" not in r.stderr
+
+
+CATALOGUE_SCRIPT = r'''
+import ctypes, sys, os, numpy as np
+sys.path.insert(0, os.path.join(os.environ["REPO"], "tests"))
+import util, inflate_catalogue as ic
+sim = util.SimCodec(ctypes.CDLL(os.environ["SIM_ASAN"]))
+cases = [c for c in ic.hand_cases() if c.name != "pair_at_every_bit_residue"]   # (256 x 3 blocks: the plain emulator runs it)
+cases += ic.mutation_catchers() + ic.sweep_cases(list(ic.sweep_combos())[5::37], 24000, every=4096)
+for c in cases:
+    got = sim.uncompress_records(c.records, len(c.words))
+    assert np.array_equal(got, c.words), c.name
+    exp = c.expected_fallbacks()
+    assert exp is None or (sim.chain_fallbacks, sim.fallbacks) == exp, c.name
+print("CATALOGUE-OK", len(cases))
+'''
+
+
+def test_conformance_catalogue_under_asan(tmp_path, asan_sim):
+    """Valid foreign streams (tests/inflate_catalogue.py: hand-built DEFLATE at the decoder's edges, other zlib parameters)
+    through the shipped-limit sanitizer build: a decoder that would read or write out of bounds, or read device memory nobody
+    wrote, on a stream zlib accepts is caught here, before it reaches a GPU."""
+    so, asan_rt = asan_sim
+    script = tmp_path / "catalogue.py"
+    script.write_text(CATALOGUE_SCRIPT)
+    env = dict(os.environ, REPO=util.ROOT, SIM_ASAN=so, LD_PRELOAD=asan_rt,
+               ASAN_OPTIONS="detect_leaks=0:detect_stack_use_after_return=0:abort_on_error=1")
+    r = subprocess.run([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
+    assert r.returncode == 0 and "CATALOGUE-OK" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+    assert "ERROR: AddressSanitizer" not in r.stderr

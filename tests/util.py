@@ -2,7 +2,9 @@
 import ctypes
 import hashlib
 import os
+import struct
 import subprocess
+import zlib
 
 import numpy as np
 
@@ -111,6 +113,59 @@ def aligned_empty(nbytes: int, align: int = 64) -> np.ndarray:
     raw = np.zeros(nbytes + align, np.uint8)
     off = (-raw.ctypes.data) % align
     return raw[off:off + nbytes]
+
+
+# ------------------------------------------------------------------ containers of foreign plane streams
+FLUSHES = {"full": zlib.Z_FULL_FLUSH, "finish": zlib.Z_FINISH, "sync": zlib.Z_SYNC_FLUSH, "partial": zlib.Z_PARTIAL_FLUSH}
+
+
+def python_zlib_stream(plane, level=6, strategy=zlib.Z_RLE, memlevel=9, wbits=15, flush="full", every=0) -> bytes:
+    """raw deflate of one plane by the system zlib.  The reference writes level 6, memLevel 9, Z_RLE and ends with
+    Z_FULL_FLUSH (zip.c:106-123); `flush` = how the stream ends ("full", "finish") or, with `every` bytes, what is flushed
+    after every piece ("sync", "partial"; the stream then ends with Z_FULL_FLUSH)."""
+    co = zlib.compressobj(level, zlib.DEFLATED, -wbits, memlevel, strategy)
+    b = plane.tobytes() if isinstance(plane, np.ndarray) else bytes(plane)
+    if not every:
+        return co.compress(b) + co.flush(FLUSHES[flush])
+    z = bytearray()
+    for a in range(0, len(b), every):
+        z += co.compress(b[a: a + every])
+        z += co.flush(FLUSHES[flush] if a + every < len(b) else zlib.Z_FULL_FLUSH)
+    return bytes(z)
+
+
+def chunk_record(planes, streams) -> bytes:
+    """one chunk record in the reference's format (workers.c:837-850): four u32 payload lengths (bit 31 = RAW), then the
+    payloads.  streams[j] is plane j's deflate stream, or None to store the plane RAW."""
+    hdr, pay = bytearray(), bytearray()
+    for p, z in zip(planes, streams):
+        if z is None:
+            hdr += struct.pack("<I", len(p) | 0x80000000)
+            pay += bytes(p)
+        else:
+            hdr += struct.pack("<I", len(z))
+            pay += z
+    return bytes(hdr + pay)
+
+
+def file_header(nbytes: int) -> bytes:
+    """the 17-byte container header (common.c:137-148): u64 fsz, u32 chk, i8 type, i8 ztypes[4]"""
+    return struct.pack("<QIb4b", nbytes, CHUNK, 0, 0, 0, 0, 0)
+
+
+def container_from_python_zlib(words, strategy, level=6, memlevel=9, wbits=15, flush="full", every=0) -> bytes:
+    """A container in the reference's format whose plane streams were written by the system zlib with other parameters
+    than the reference's (general distances / fixed codes / Huffman only / other flushes): exercises the decoder's fallback
+    paths (SURVEY 8(f)-4 decoder tolerance).  A plane is stored RAW where the reference would (len(plane) <= len(z) + 4)."""
+    n = len(words)
+    b = words.view(np.uint8).reshape(-1, 4)
+    out = bytearray(file_header(4 * n))
+    for c0 in range(0, n, CHUNK):
+        c1 = min(n, c0 + CHUNK)
+        planes = [np.ascontiguousarray(b[c0:c1, j]) for j in range(4)]
+        zs = [python_zlib_stream(p, level, strategy, memlevel, wbits, flush, every) for p in planes]
+        out += chunk_record(planes, [z if len(p) > len(z) + 4 else None for p, z in zip(planes, zs)])
+    return bytes(out)
 
 
 # ------------------------------------------------------------------ oracle
