@@ -17,6 +17,12 @@ class MrczBoxGeom(ctypes.Structure):
                 ("bx", ctypes.c_uint32), ("by", ctypes.c_uint32), ("bz", ctypes.c_uint32), ("fill_bits", ctypes.c_uint32)]
 
 
+class MrczBinGeom(ctypes.Structure):
+    """mrcz_bin_geom_t: a float32 volume of nx x ny x nz words from file word data_word0, binned by fx x fy x fz"""
+    _fields_ = [("data_word0", ctypes.c_uint64), ("nx", ctypes.c_uint32), ("ny", ctypes.c_uint32), ("nz", ctypes.c_uint32),
+                ("fx", ctypes.c_uint32), ("fy", ctypes.c_uint32), ("fz", ctypes.c_uint32)]
+
+
 def load():
     if not os.path.exists(LIB_PATH):
         raise MrczLibraryMissing(
@@ -56,6 +62,13 @@ def load():
     lib.mrcz_boxes_chunks.argtypes = [geom, vp, u32, u64, u32, vp]
     lib.mrcz_uncompress_boxes.restype = i32
     lib.mrcz_uncompress_boxes.argtypes = [vp, vp, u64, u64, u32, u64, u64, geom, vp, u32, vp, i32, ctypes.POINTER(u64)]
+    bgeom = ctypes.POINTER(MrczBinGeom)
+    lib.mrcz_bin_chunks.restype = i32
+    lib.mrcz_bin_chunks.argtypes = [bgeom, u64, u32, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.mrcz_uncompress_binned.restype = i32
+    lib.mrcz_uncompress_binned.argtypes = [vp, vp, u64, u64, u32, u64, u64, bgeom, vp, i32, ctypes.POINTER(u64)]
+    lib.mrcz_binned_finish.restype = i32
+    lib.mrcz_binned_finish.argtypes = [vp, bgeom, vp, vp]
     lib.mrcz_generate_kat_words.restype = i32
     lib.mrcz_generate_kat_words.argtypes = [vp, vp, u64, u64]
     lib.mrcz_set_ztypes.restype = i32
@@ -84,4 +97,5 @@ EXPORTS = [
     "mrcz_set_ztypes", "mrcz_generate_kat_words", "mrcz_err_hist", "mrcz_err_collect", "mrcz_compress_chunks_int8", "mrcz_uncompress_chunks_int8", "mrcz_compress_chunks_int8_async", "mrcz_uncompress_chunks_int8_async",
     "mrcz_record_size", "mrcz_records_index", "mrcz_uncompress_range", "mrcz_uncompress_range_async",
     "mrcz_box_origins", "mrcz_boxes_chunks", "mrcz_uncompress_boxes",
+    "mrcz_bin_chunks", "mrcz_uncompress_binned", "mrcz_binned_finish",
 ]

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MrczBoxGeom
+from ._lib import MrczBinGeom, MrczBoxGeom
 
 CHUNK_FLOATS = 6 * 1048576  # src/include/constant.h:25
 FILE_HEADER_BYTES = 17      # src/core/common.c:137-148
@@ -47,6 +47,7 @@ class MrcZipCodec:
         if not torch.cuda.is_available():
             raise MrczError("no HIP device visible: the codec has no CPU path")
         self.device = torch.device("cuda", device if isinstance(device, int) else device.index)
+        self.max_batch_chunks = max_batch_chunks
         self._ctx = ctypes.c_void_p()
         rc = _LIB.mrcz_create(ctypes.byref(self._ctx), self.device.index, max_batch_chunks)
         if rc != 0:
@@ -174,6 +175,40 @@ class MrcZipCodec:
         if rc != 0:
             raise self._err("mrcz_uncompress_boxes", rc)
         return out, int(decoded.value)
+
+    def uncompress_binned_device(self, records: torch.Tensor, nfloats_file: int, geom: MrczBinGeom, acc: torch.Tensor, first_chunk: int = 0,
+                                 nchunks: int = None, int_mode: bool = False, chk: int = CHUNK_FLOATS):
+        """binned decode, one step (mrcz_uncompress_binned): `records` (cuda uint8) = the chunk records of chunks [first_chunk,
+        first_chunk + nchunks) of a file of nfloats_file floats (default: every chunk from first_chunk on).  Folds the voxels of
+        the chunks of mrcz_bin_chunks' [c0, c1) among them into `acc`, an (mz, my, mx) float64 cuda tensor of partial sums (no
+        zeroing needed); the other chunks are only walked.  Steps cover [c0, c1) in increasing chunk order, each chunk once;
+        then binned_finish_device.  Returns chunks decoded."""
+        assert records.is_cuda and records.dtype == torch.uint8 and records.is_contiguous()
+        nbins = (geom.nz // geom.fz) * (geom.ny // geom.fy) * (geom.nx // geom.fx) if min(geom.fx, geom.fy, geom.fz) else 0
+        assert acc.is_cuda and acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() >= nbins
+        if nchunks is None:
+            nchunks = max((nfloats_file + chk - 1) // chk - first_chunk, 0)
+        torch.cuda.current_stream(records.device).synchronize()
+        decoded = ctypes.c_uint64()
+        rc = _LIB.mrcz_uncompress_binned(self._ctx, records.data_ptr(), records.numel(), nfloats_file, chk, first_chunk, nchunks,
+                                         ctypes.byref(geom), acc.data_ptr(), 1 if int_mode else 0, ctypes.byref(decoded))
+        if rc != 0:
+            raise self._err("mrcz_uncompress_binned", rc)
+        return int(decoded.value)
+
+    def binned_finish_device(self, geom: MrczBinGeom, acc: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+        """the binned volume (mrcz_binned_finish): (float)(acc / (fx fy fz)) as an (mz, my, mx) float32 cuda tensor (`out`, or
+        allocated when None)"""
+        shape = (geom.nz // geom.fz, geom.ny // geom.fy, geom.nx // geom.fx) if min(geom.fx, geom.fy, geom.fz) else (0, 0, 0)
+        assert acc.is_cuda and acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() >= shape[0] * shape[1] * shape[2]
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=acc.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= shape[0] * shape[1] * shape[2]
+        torch.cuda.current_stream(acc.device).synchronize()
+        rc = _LIB.mrcz_binned_finish(self._ctx, ctypes.byref(geom), acc.data_ptr(), out.data_ptr())
+        if rc != 0:
+            raise self._err("mrcz_binned_finish", rc)
+        return out
 
     def erase_bits_device(self, words: torch.Tensor, bits: int, first_word_index: int = 0):
         assert words.is_cuda and words.element_size() == 4
@@ -375,3 +410,51 @@ class MrcZipCodec:
                 self.uncompress_boxes_device(torch.empty(16, dtype=torch.uint8, device=self.device), nfl, geom, org, nchunks=0,
                                              out=out, chk=chk)
         return out.view(torch.float32)
+
+    def read_mrc_binned(self, path_or_bytes, factor, mode: str = "float") -> torch.Tensor:
+        """a compressed float32 (mode 2) MRC volume average-pooled by `factor` (an int or (fx, fy, fz)), as an (mz, my, mx) =
+        (nz // fz, ny // fy, nx // fx) float32 cuda tensor; voxels of a trailing remainder of an axis are ignored.  Each mean is
+        the float64 sum of the bin's voxels in file order over fx fy fz, narrowed to float32 (mrcz_uncompress_binned).  Reads the
+        file header, the chunk headers up to the last chunk the bins use, then the records of the used chunks in pieces of at
+        most max_batch_chunks chunks, one decode call per piece: neither host nor device holds the whole container, and the
+        device holds no buffer of the volume's size."""
+        if mode not in ("float", "int"):
+            raise MrczError("mode must be 'float' or 'int' (mrc_tar -s)")
+        f3 = (int(factor),) * 3 if np.ndim(factor) == 0 else tuple(int(v) for v in factor)
+        if len(f3) != 3:
+            raise MrczError(f"bin factor {factor}: want an int or (fx, fy, fz)")
+        fx, fy, fz = f3
+        with self._open(path_or_bytes) as f:
+            nfl, chk = self._container_header(f)
+            d0, nx, ny, nz = self._mrc_volume(f)
+            if d0 + nx * ny * nz > nfl:
+                raise MrczError("the MRC header describes more data than the file holds")
+            if not (1 <= fx <= nx and 1 <= fy <= ny and 1 <= fz <= nz) or fx * fy * fz > 1 << 31:
+                raise MrczError(f"bin factor {(fx, fy, fz)} outside 1 .. {(nx, ny, nz)} (or a bin of more than 2^31 voxels)")
+            geom = MrczBinGeom(d0, nx, ny, nz, fx, fy, fz)
+            c0, c1 = ctypes.c_uint64(), ctypes.c_uint64()
+            if _LIB.mrcz_bin_chunks(ctypes.byref(geom), nfl, chk, ctypes.byref(c0), ctypes.byref(c1)) != 0:
+                raise MrczError("bin geometry refused")
+            c0, c1 = int(c0.value), int(c1.value)
+            # record offsets from the chunk headers, up to c1 (nothing behind it is read)
+            offs, off, size_ = [], FILE_HEADER_BYTES, ctypes.c_uint64()
+            for c in range(c1):
+                offs.append(off)
+                f.seek(off)
+                h = f.read(16)
+                if len(h) < 16 or _LIB.mrcz_record_size(h, min(chk, nfl - c * chk), ctypes.byref(size_)) != 0:
+                    raise MrczError(f"damaged or truncated container: chunk header {c} at byte {off}")
+                off += size_.value
+            offs.append(off)
+            acc = torch.empty((nz // fz, ny // fy, nx // fx), dtype=torch.float64, device=self.device)
+            step = max(int(self.max_batch_chunks), 1)
+            for k in range(c0, c1, step):
+                e = min(k + step, c1)
+                f.seek(offs[k])
+                body = f.read(offs[e] - offs[k])
+                if len(body) != offs[e] - offs[k]:
+                    raise MrczError("truncated container: the records of the binned chunks end early")
+                rec = torch.frombuffer(bytearray(body), dtype=torch.uint8).to(self.device)
+                self.uncompress_binned_device(rec, nfl, geom, acc, first_chunk=k, nchunks=e - k, int_mode=(mode == "int"), chk=chk)
+                del rec
+        return self.binned_finish_device(geom, acc)

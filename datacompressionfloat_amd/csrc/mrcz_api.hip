@@ -90,7 +90,7 @@ struct mrcz_ctx {
     uint32_t lz4_planes;   /* bit j: byte stream j of the containers to decode holds LZ4 blocks (mrcz_set_ztypes) */
     unsigned long long *errhist; /* erroranalysis: 2048 histogram bins + the candidate counter; allocated on first use */
     uint8_t *planes;       /* byte planes of one batch (stream s at s * CHK), both directions; allocated on first use */
-    uint32_t *stage;       /* box decode: the words of one batch (max_chunks x CHK); allocated on first use */
+    uint32_t *stage;       /* box and binned decode: the words of one batch (max_chunks x CHK); allocated on first use */
     uint32_t *boxbuf;      /* box decode: origins and box lists of a call (boxbuf_words words) */
     uint64_t boxbuf_words;
     /* timing */
@@ -752,6 +752,9 @@ extern "C" int mrcz_uncompress_range_async(mrcz_ctx_t *ctx, const void *d_record
 
 /* ---- box decode: boxes of a float32 volume out of the records of the chunks they touch ---- */
 #include "mrcz_boxes.hip"
+
+/* ---- binned decode: an average-pooled float32 volume, the chunks streamed through the staging buffer ---- */
+#include "mrcz_binned.hip"
 
 /* ---- events and the three streams of a context (pipelines: include/mrcz_hip.h) ---- */
 struct mrcz_event { hipEvent_t ev; };

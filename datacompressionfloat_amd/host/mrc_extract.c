@@ -1,8 +1,9 @@
 /*
- * mrc_extract.c -- range and box decode from the command line: part of a container without reading or decoding the rest.
+ * mrc_extract.c -- range, box and binned decode from the command line: part of a container without reading or decoding the rest,
+ * or a binned overview of it without a buffer of the volume's size.
  *
- *   mrc_extract -i vol.mrc.zip -o out.raw (-w first:count | -z z0:z1 | -B centers.txt -S bx[,by,bz] [-F fill]) [-s float|int]
- *               [-g device]
+ *   mrc_extract -i vol.mrc.zip -o out.raw (-w first:count | -z z0:z1 | -B centers.txt -S bx[,by,bz] [-F fill] | -N f[,fy,fz])
+ *               [-s float|int] [-g device]
  *
  *   -w first:count   words [first, first + count) of the decoded file (4 bytes each)
  *   -z z0:z1         sections [z0, z1) of a float32 (mode 2) MRC volume: nx, ny, nz, mode (bytes 0-15) and nsymbt (bytes 92-95)
@@ -12,13 +13,18 @@
  *                    is raw float32 in [N][bz][by][bx] order
  *   -S bx[,by,bz]    box size (one number: a cube)
  *   -F fill          value of the voxels outside the volume, default 0
+ *   -N f | fx,fy,fz  a float32 MRC volume average-pooled by the bin factors (1 <= f <= the dimension; voxels of a trailing
+ *                    remainder of an axis are ignored).  The output is raw float32 in [mz][my][mx] order, (mx, my, mz) =
+ *                    (nx / fx, ny / fy, nz / fz): each voxel is the mean of its bin, summed in double in file order
  *   -s               decode mode, as mrc_tar -s (the container does not record it)
  *
  * The 17-byte file header and the 16-byte header of every chunk before the window are read with pread; then only the records of
  * the chunks that cover the window, which mrcz_uncompress_range decodes (in one call: the covering records and the window must
  * fit in device memory; the workspace is batched as in every decode).  -B reads the chunk headers up to the last chunk a box
- * touches (mrcz_boxes_chunks), then the records of every run of touched chunks, one mrcz_uncompress_boxes call per run.  Not one
- * of the reference's front ends: mrc_tar and mrc_tarx keep the reference's command lines.
+ * touches (mrcz_boxes_chunks), then the records of every run of touched chunks, one mrcz_uncompress_boxes call per run.  -N reads
+ * the chunk headers up to the last chunk the bins use (mrcz_bin_chunks), then the records of the used chunks in pieces of at
+ * most the context's batch (16 chunks), one mrcz_uncompress_binned call per piece, and one mrcz_binned_finish.  Not one of the
+ * reference's front ends: mrc_tar and mrc_tarx keep the reference's command lines.
  */
 #include "../../include/mrcz_hip.h"
 
@@ -35,8 +41,8 @@
 
 static void usage(const char *prog)
 {
-    printf("\nUsage:\n\n\t%s -i <container> -o <output file> (-w <first>:<count> | -z <z0>:<z1> | -B <centres> -S <bx>[,<by>,<bz>] [-F <fill>])\n"
-           "\t\t[-s float|int] [-g device]\nwhere:\n", prog);
+    printf("\nUsage:\n\n\t%s -i <container> -o <output file> (-w <first>:<count> | -z <z0>:<z1> | -B <centres> -S <bx>[,<by>,<bz>] [-F <fill>]\n"
+           "\t\t| -N <f>[,<fy>,<fz>]) [-s float|int] [-g device]\nwhere:\n", prog);
     printf("\t-i\tcontainer written by mrc_tar -t zip\n\n");
     printf("\t-o\traw output: the decoded words of the window, 4 bytes each\n\n");
     printf("\t-w\twords [first, first + count) of the decoded file\n\n");
@@ -45,6 +51,8 @@ static void usage(const char *prog)
            "\t\toutput: raw float32, [N][bz][by][bx]\n\n");
     printf("\t-S\tbox size with -B: bx, or bx,by,bz\n\n");
     printf("\t-F\tvalue of box voxels outside the volume, default 0\n\n");
+    printf("\t-N\ta float32 (mode 2) MRC volume binned (average-pooled) by f, or by fx,fy,fz; remainders are ignored;\n"
+           "\t\toutput: raw float32, [nz / fz][ny / fy][nx / fx]\n\n");
     printf("\t-s\tdata type the container was written with, [float | int], default float\n\n");
     printf("\t-g\tHIP device, default 0\n\n");
 }
@@ -136,15 +144,15 @@ static void mrc_volume(mrcz_ctx_t **pc, int device, const struct container *ct, 
     g->nx = (uint32_t)nx; g->ny = (uint32_t)ny; g->nz = (uint32_t)nz;
 }
 
-/* -S bx or bx,by,bz */
-static int parse_size(const char *s, uint32_t sz[3])
+/* -S bx or bx,by,bz (each 1 .. max); -N likewise */
+static int parse_size(const char *s, uint32_t sz[3], unsigned long long max)
 {
     for (int k = 0; k < 3; k++) {
         char *e = NULL;
         if (*s < '0' || *s > '9') return -1;
         errno = 0;
         const unsigned long long v = strtoull(s, &e, 10);
-        if (errno || v == 0 || v > 65536u) return -1;
+        if (errno || v == 0 || v > max) return -1;
         sz[k] = (uint32_t)v;
         if (k == 0 && *e == 0) { sz[1] = sz[2] = sz[0]; return 0; }
         if (k < 2 ? *e != ',' : *e != 0) return -1;
@@ -251,12 +259,55 @@ static uint32_t *decode_boxes(mrcz_ctx_t *c, const struct container *ct, mrcz_bo
     return out;
 }
 
+/* the volume of g binned, decoded on the device, into a malloc'ed host buffer of mz * my * mx floats */
+static float *decode_binned(mrcz_ctx_t *c, const struct container *ct, const mrcz_bin_geom_t *g, uint32_t batch, int int_mode)
+{
+    const uint64_t chk = ct->chk, nbins = (uint64_t)(g->nx / g->fx) * (g->ny / g->fy) * (g->nz / g->fz);
+    uint64_t c0 = 0, c1 = 0;
+    if (mrcz_bin_chunks(g, ct->nfl, ct->chk, &c0, &c1) != MRCZ_OK) die("bin geometry", NULL);
+    uint64_t *offs = (uint64_t *)malloc(8u * (size_t)(c1 + 1));
+    float *out = (float *)malloc(4u * (size_t)nbins);
+    if (!offs || !out) die("out of memory", NULL);
+    uint64_t off = MRCZ_FILE_HEADER_BYTES, biggest = 0;
+    for (uint64_t k = 0; k < c1; k++) { /* 16 bytes per chunk up to the last used one, nothing behind it */
+        uint8_t h[16];
+        uint64_t bytes = 0;
+        const uint64_t left = ct->nfl - k * chk;
+        offs[k] = off;
+        pread_all(ct->fd, h, 16, off, "truncated container (chunk header)");
+        if (mrcz_record_size(h, (uint32_t)(left < chk ? left : chk), &bytes) != MRCZ_OK) die("damaged chunk header", NULL);
+        off += bytes;
+    }
+    offs[c1] = off;
+    for (uint64_t k = c0; k < c1; k += batch) { /* the largest piece sizes the record buffers */
+        const uint64_t e = k + batch < c1 ? k + batch : c1;
+        if (offs[e] - offs[k] > biggest) biggest = offs[e] - offs[k];
+    }
+    void *h_rec = NULL, *d_rec = NULL, *d_acc = NULL, *d_out = NULL;
+    if (mrcz_dev_malloc(c, &d_acc, 8 * nbins) || mrcz_dev_malloc(c, &d_out, 4 * nbins)) die("out of device memory", c);
+    if (mrcz_host_malloc(c, &h_rec, biggest) || mrcz_dev_malloc(c, &d_rec, biggest)) die("out of memory", c);
+    for (uint64_t k = c0; k < c1; k += batch) { /* one read and one decode call per piece of at most `batch` chunks */
+        const uint64_t e = k + batch < c1 ? k + batch : c1, len = offs[e] - offs[k];
+        pread_all(ct->fd, h_rec, len, offs[k], "truncated container (payload)");
+        if (mrcz_copy_h2d(c, d_rec, h_rec, len) != MRCZ_OK) die("copy to the device", c);
+        if (mrcz_uncompress_binned(c, d_rec, len, ct->nfl, ct->chk, k, e - k, g, (double *)d_acc, int_mode, NULL) != MRCZ_OK) die("binned decode", c);
+    }
+    if (mrcz_binned_finish(c, g, (const double *)d_acc, (float *)d_out) != MRCZ_OK) die("binned finish", c);
+    if (mrcz_copy_d2h(c, out, d_out, 4 * nbins) != MRCZ_OK) die("copy from the device", c);
+    mrcz_dev_free(c, d_out);
+    mrcz_dev_free(c, d_acc);
+    mrcz_dev_free(c, d_rec);
+    mrcz_host_free(c, h_rec);
+    free(offs);
+    return out;
+}
+
 int main(int argc, char *argv[])
 {
-    const char *in = NULL, *outp = NULL, *wspec = NULL, *zspec = NULL, *bspec = NULL, *sspec = NULL, *fspec = NULL, *dtype = "float";
+    const char *in = NULL, *outp = NULL, *wspec = NULL, *zspec = NULL, *bspec = NULL, *sspec = NULL, *fspec = NULL, *nspec = NULL, *dtype = "float";
     int opt, device = 0;
     if (argc < 2) { usage(argv[0]); return 255; }
-    while ((opt = getopt(argc, argv, "hi:o:w:z:B:S:F:s:g:")) != -1) {
+    while ((opt = getopt(argc, argv, "hi:o:w:z:B:S:F:N:s:g:")) != -1) {
         switch (opt) {
         case 'i': in = optarg; break;
         case 'o': outp = optarg; break;
@@ -265,22 +316,25 @@ int main(int argc, char *argv[])
         case 'B': bspec = optarg; break;
         case 'S': sspec = optarg; break;
         case 'F': fspec = optarg; break;
+        case 'N': nspec = optarg; break;
         case 's': dtype = optarg; break;
         case 'g': device = atoi(optarg); break;
         case 'h': usage(argv[0]); return 0;
         default: usage(argv[0]); return 255;
         }
     }
-    if (!in || !outp || !!wspec + !!zspec + !!bspec != 1) { usage(argv[0]); die("need -i, -o and one of -w, -z, -B", NULL); }
+    if (!in || !outp || !!wspec + !!zspec + !!bspec + !!nspec != 1) { usage(argv[0]); die("need -i, -o and one of -w, -z, -B, -N", NULL); }
     if (!bspec && (sspec || fspec)) die("-S and -F go with -B", NULL);
     const int int_mode = strcmp(dtype, "int") == 0;
     if (!int_mode && strcmp(dtype, "float") != 0) die("-s must be float or int", NULL);
     uint64_t a = 0, b = 0;
-    uint32_t bsize[3] = {0, 0, 0};
+    uint32_t bsize[3] = {0, 0, 0}, bin[3] = {0, 0, 0};
     float fill = 0.f;
-    if (bspec) {
+    if (nspec) {
+        if (parse_size(nspec, bin, 0xffffffffull)) die("-N wants f or fx,fy,fz (each at least 1)", NULL);
+    } else if (bspec) {
         if (!sspec) die("-B needs a box size (-S bx or -S bx,by,bz)", NULL);
-        if (parse_size(sspec, bsize)) die("-S wants bx or bx,by,bz (each 1 .. 65536)", NULL);
+        if (parse_size(sspec, bsize, 65536u)) die("-S wants bx or bx,by,bz (each 1 .. 65536)", NULL);
         if (fspec) {
             char *e = NULL;
             fill = strtof(fspec, &e);
@@ -303,6 +357,35 @@ int main(int argc, char *argv[])
         if (ct.ztypes[j] != 0 && ct.ztypes[j] != 2 && ct.ztypes[j] != 4) die("unknown byte stream compressor type in the file header", NULL);
 
     mrcz_ctx_t *c = NULL;
+    if (nspec) {
+        if (ct.nfl == 0) die("empty container", NULL);
+        mrcz_box_geom_t v;
+        mrc_volume(&c, device, &ct, &v); /* (a context of one chunk's batch for the header; the binned pieces get their own) */
+        if (v.data_word0 + (uint64_t)v.nx * v.ny * v.nz > ct.nfl) die("the MRC header describes more data than the file holds", NULL);
+        mrcz_bin_geom_t g;
+        g.data_word0 = v.data_word0;
+        g.nx = v.nx; g.ny = v.ny; g.nz = v.nz;
+        g.fx = bin[0]; g.fy = bin[1]; g.fz = bin[2];
+        if (g.fx > g.nx || g.fy > g.ny || g.fz > g.nz) die("-N: a bin factor is larger than the volume's dimension", NULL);
+        if ((uint64_t)g.fx * g.fy * g.fz > 0x80000000ull) die("-N: a bin of more than 2^31 voxels", NULL);
+        uint64_t c0 = 0, c1 = 0;
+        if (mrcz_bin_chunks(&g, ct.nfl, ct.chk, &c0, &c1) != MRCZ_OK) die("bin geometry", NULL);
+        const uint32_t batch = (uint32_t)(c1 - c0 < 16 ? c1 - c0 : 16);
+        mrcz_destroy(c);
+        if (mrcz_create(&c, device, batch) != MRCZ_OK) die("no usable HIP device (the codec has no CPU path)", NULL);
+        if (mrcz_set_ztypes(c, ct.ztypes) != MRCZ_OK) die("byte stream compressor types", c);
+        float *out = decode_binned(c, &ct, &g, batch, int_mode);
+        const size_t words = (size_t)(g.nx / g.fx) * (g.ny / g.fy) * (g.nz / g.fz);
+        FILE *fo = fopen(outp, "wb");
+        if (!fo) die("cannot open the output file", NULL);
+        if (fwrite(out, 4, words, fo) != words || fclose(fo) != 0) die("write", NULL);
+        printf("%u x %u x %u volume binned by %u x %u x %u: %u x %u x %u written to %s\n", g.nx, g.ny, g.nz, g.fx, g.fy, g.fz, g.nx / g.fx,
+               g.ny / g.fy, g.nz / g.fz, outp);
+        free(out);
+        close(ct.fd);
+        fflush(stdout);
+        _exit(0);
+    }
     if (bspec) {
         uint32_t n = 0;
         double *centres = read_centres(bspec, &n);

@@ -208,6 +208,37 @@ int mrcz_uncompress_boxes(mrcz_ctx_t *ctx, const void *d_records, uint64_t len, 
                           uint64_t first_chunk, uint64_t nchunks, const mrcz_box_geom_t *g, const int32_t *h_origins,
                           uint32_t nboxes, void *d_out, int int_mode, uint64_t *chunks_decoded);
 
+/*
+ * Binned decode: a float32 volume average-pooled by (fx, fy, fz), decoded chunk by chunk without a buffer of the volume's size.
+ * The volume is as in box decode (voxel (x, y, z) = file word data_word0 + (z * ny + y) * nx + x).  The output is
+ * mz x my x mx = (nz / fz) x (ny / fy) x (nx / fx) float32 (integer division: the voxels of a trailing remainder of any axis
+ * are ignored).  Output voxel (X, Y, Z) is the mean of its fx * fy * fz voxels: they are widened to double and added in file
+ * order (z, then y, then x), the sum starting from the first voxel; then (float)(sum / (double)(fx * fy * fz)).  So factor
+ * (1, 1, 1) gives back every non-NaN word bit for bit, and the result does not depend on how the chunks are cut into calls.
+ *   mrcz_bin_chunks         (host) chunks [c0, c1) hold the used voxels: from the chunk of the first to the chunk of the last
+ *   mrcz_uncompress_binned  d_records/len = the records of chunks [first_chunk, first_chunk + nchunks) of the file.  Chunks
+ *                           of [c0, c1) among them are decoded once, in runs of up to max_batch_chunks, and their voxels
+ *                           folded into d_acc (mz * my * mx doubles, the caller's, 16-byte aligned: the partial sums); the
+ *                           other chunks are only walked (16-byte header).  int_mode and mrcz_set_ztypes apply as in range
+ *                           decode.  chunks_decoded (optional) = chunks decoded.  Synchronous.
+ *   mrcz_binned_finish      d_out[i] = (float)(d_acc[i] / (fx * fy * fz)), mz * my * mx floats.  Synchronous.
+ * Contract: a binned volume is one or more mrcz_uncompress_binned calls that together cover [c0, c1) in increasing chunk order,
+ * each chunk once, then one mrcz_binned_finish.  d_acc needs no zeroing (a bin's first voxel assigns its sum); between the
+ * calls it must be left alone.  MRCZ_EINVAL: a factor of 0 or larger than its dimension, a volume that does not fit in
+ * nfloats_file, a bin of more than 2^31 voxels, a NULL pointer, first_chunk + nchunks past the file; MRCZ_EFORMAT: records that
+ * end before the last chunk's record does (never read past len).
+ */
+typedef struct mrcz_bin_geom {
+    uint64_t data_word0;  /* file word of voxel (0, 0, 0) */
+    uint32_t nx, ny, nz;  /* volume, each >= 1 */
+    uint32_t fx, fy, fz;  /* bin factors, 1 <= f <= dimension */
+} mrcz_bin_geom_t;
+int mrcz_bin_chunks(const mrcz_bin_geom_t *g, uint64_t nfloats_file, uint32_t chk, uint64_t *c0, uint64_t *c1);
+int mrcz_uncompress_binned(mrcz_ctx_t *ctx, const void *d_records, uint64_t len, uint64_t nfloats_file, uint32_t chk,
+                           uint64_t first_chunk, uint64_t nchunks, const mrcz_bin_geom_t *g, double *d_acc,
+                           int int_mode, uint64_t *chunks_decoded);
+int mrcz_binned_finish(mrcz_ctx_t *ctx, const mrcz_bin_geom_t *g, const double *d_acc, float *d_out);
+
 /* apply_mask alone on device (the erasebytes restatement used by the GPU-side verification tools,
  * src/tool/erasebytes.c:109-134): words [256, nwords) of a file &= mask(bits).  In place. */
 int mrcz_erase_bits(mrcz_ctx_t *ctx, void *d_words, uint64_t nwords, uint64_t first_word_index, int bits);
