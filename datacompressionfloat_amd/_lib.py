@@ -49,6 +49,8 @@ def load():
     lib.mrcz_compress_chunks_int8.argtypes = [vp, vp, u64, u64, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.mrcz_uncompress_chunks_int8.restype = i32
     lib.mrcz_uncompress_chunks_int8.argtypes = [vp, vp, u64, u64, u32, u64, vp, ctypes.POINTER(u64)]
+    lib.mrcz_compress_chunks_abs.restype = i32
+    lib.mrcz_compress_chunks_abs.argtypes = [vp, vp, u64, u64, ctypes.c_float, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.mrcz_record_size.restype = i32
     lib.mrcz_record_size.argtypes = [vp, u32, ctypes.POINTER(u64)]
     lib.mrcz_records_index.restype = i32
@@ -75,6 +77,8 @@ def load():
     lib.mrcz_set_ztypes.argtypes = [vp, ctypes.c_char_p]
     lib.mrcz_erase_bits.restype = i32
     lib.mrcz_erase_bits.argtypes = [vp, vp, u64, u64, i32]
+    lib.mrcz_erase_abs.restype = i32
+    lib.mrcz_erase_abs.argtypes = [vp, vp, u64, u64, ctypes.c_float]
     lib.mrcz_set_timing.restype = i32
     lib.mrcz_set_timing.argtypes = [vp, i32]
     lib.mrcz_last_timings.restype = i32
@@ -98,4 +102,5 @@ EXPORTS = [
     "mrcz_record_size", "mrcz_records_index", "mrcz_uncompress_range", "mrcz_uncompress_range_async",
     "mrcz_box_origins", "mrcz_boxes_chunks", "mrcz_uncompress_boxes",
     "mrcz_bin_chunks", "mrcz_uncompress_binned", "mrcz_binned_finish",
+    "mrcz_compress_chunks_abs", "mrcz_compress_chunks_abs_async", "mrcz_erase_abs",
 ]

@@ -27,6 +27,23 @@ class MrczError(RuntimeError):
     pass
 
 
+_FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def abs_bound(eps) -> float:
+    """An absolute-error bound as the codec takes it: float32, rounded toward zero so that the bound also holds for the value
+    given.  Raises MrczError unless it is finite and > 0."""
+    e = float(eps)
+    if not (np.isfinite(e) and e > 0):
+        raise MrczError("absolute error bound must be finite and > 0")
+    f = np.float32(min(e, _FLT_MAX))
+    if float(f) > e:
+        f = np.nextafter(f, np.float32(0))
+    if not f > 0:
+        raise MrczError("absolute error bound below the smallest float32")
+    return float(f)
+
+
 def pack_file_header(fsz: int) -> bytes:
     """write_mrczip_header (src/core/common.c:137-148): u64 fsz, u32 chk, i8 type, i8 ztypes[4]."""
     return struct.pack("<QIb4b", fsz, CHUNK_FLOATS, 0, 0, 0, 0, 0)
@@ -92,11 +109,18 @@ class MrcZipCodec:
         return int(_LIB.mrcz_records_bound(nfloats))
 
     # ---- device-resident API (what bench.py times) ----
-    def compress_device(self, words: torch.Tensor, bits: int, first_chunk: int = 0, out: torch.Tensor = None, int_mode: bool = False):
+    def compress_device(self, words: torch.Tensor, bits: int, first_chunk: int = 0, out: torch.Tensor = None, int_mode: bool = False,
+                        abs_err=None):
         """words: cuda tensor of 32-bit elements (int32/float32/uint32 view), chunk-aligned start.
         int_mode = the reference's "-s int" (src/core/workers.c:125-175): bits is ignored.
+        abs_err = eps: absolute-error mode (mrcz_compress_chunks_abs), every decoded float within eps of the original; needs
+        bits == 0 and no int_mode.
         Returns (records uint8 cuda tensor view, plane_bytes[4])."""
         assert words.is_cuda and words.is_contiguous() and words.element_size() == 4
+        if abs_err is not None:
+            if bits != 0 or int_mode:
+                raise MrczError("abs_err excludes bits != 0 and the int mode")
+            abs_err = abs_bound(abs_err)
         n = words.numel()
         cap = self.records_bound(n)
         if out is None:
@@ -108,6 +132,9 @@ class MrcZipCodec:
         if int_mode:
             rc = _LIB.mrcz_compress_chunks_int8(self._ctx, words.data_ptr(), n, first_chunk, out.data_ptr(), out.numel(),
                                                 ctypes.byref(olen), planes)
+        elif abs_err is not None:
+            rc = _LIB.mrcz_compress_chunks_abs(self._ctx, words.data_ptr(), n, first_chunk, abs_err, out.data_ptr(), out.numel(),
+                                               ctypes.byref(olen), planes)
         else:
             rc = _LIB.mrcz_compress_chunks(self._ctx, words.data_ptr(), n, first_chunk, bits, out.data_ptr(), out.numel(),
                                            ctypes.byref(olen), planes)
@@ -218,6 +245,17 @@ class MrcZipCodec:
             raise self._err("mrcz_erase_bits", rc)
         return words
 
+    def erase_abs_device(self, words: torch.Tensor, eps, first_word_index: int = 0):
+        """what a container of compress_device(abs_err=eps) decodes to, in place: words at file index >= 256 rounded
+        (mrcz_erase_abs); `words` holds file words first_word_index, ..."""
+        assert words.is_cuda and words.element_size() == 4
+        eps = abs_bound(eps)
+        torch.cuda.current_stream(words.device).synchronize()
+        rc = _LIB.mrcz_erase_abs(self._ctx, words.data_ptr(), words.numel(), first_word_index, eps)
+        if rc != 0:
+            raise self._err("mrcz_erase_abs", rc)
+        return words
+
     def generate_kat_device(self, words: torch.Tensor, first_index: int = 0):
         """fill `words` (cuda, 32-bit elements) with words [first_index, ...) of the SURVEY App. D integer generator"""
         assert words.is_cuda and words.is_contiguous() and words.element_size() == 4
@@ -228,19 +266,24 @@ class MrcZipCodec:
         return words
 
     # ---- file-image API: same bytes as `mrc_tar_c -t zip|unzip` reads/writes ----
-    def zip_bytes(self, data: bytes, bits: int, mode: str = "float") -> bytes:
-        """run_compress on an in-memory file image (src/core/workers.c:690-881); mode = dataConvertedType ("float" | "int")."""
+    def zip_bytes(self, data: bytes, bits: int, mode: str = "float", abs_err=None) -> bytes:
+        """run_compress on an in-memory file image (src/core/workers.c:690-881); mode = dataConvertedType ("float" | "int").
+        abs_err = eps: absolute-error mode (mrc_tar -e), with bits = 0 and mode "float" only; decoding needs nothing."""
         if mode not in ("float", "int"):
             raise MrczError("mode must be 'float' or 'int' (mrc_tar -s)")
         if bits < 0 or bits > 32:
             raise MrczError("bits must be in 0..32 (src/core/workers.c:29-37 has 33 table entries)")
+        if abs_err is not None:
+            if bits != 0 or mode == "int":
+                raise MrczError("abs_err excludes bits != 0 and mode 'int' (mrc_tar -e excludes -b and -s int)")
+            abs_err = abs_bound(abs_err)
         fsz = len(data)
         nfl = fsz // 4
         if nfl == 0:
             return b""  # src/core/workers.c:757: nothing is written when the first read is empty
         host = torch.frombuffer(bytearray(data[: nfl * 4]), dtype=torch.int32)
         dev = host.to(self.device)
-        rec, _ = self.compress_device(dev, bits, 0, int_mode=(mode == "int"))
+        rec, _ = self.compress_device(dev, bits, 0, int_mode=(mode == "int"), abs_err=abs_err)
         return pack_file_header(fsz) + rec.cpu().numpy().tobytes()
 
     def unzip_bytes(self, container: bytes, mode: str = "float") -> bytes:

@@ -324,6 +324,19 @@ extern "C" int mrcz_last_timings(const mrcz_ctx_t *ctx, const char **names, floa
 
 static uint32_t mask_of(int bits) { return bits >= 32 ? 0u : (0xFFFFFFFFu << bits); } /* workers.c:29-37 */
 
+/* (q, E) of abs_round (mrcz_tile.h) for a bound eps: q = floor(log2(eps)) -- the biased exponent minus 127, or
+ * -150 + bit_length(bits) for a denormal -- and E = bits(eps).  eps must be finite and > 0. */
+static int abs_err_param(mrcz_ctx *ctx, float eps, AbsErr *ae)
+{
+    if (!(eps > 0.0f) || !isfinite(eps)) return fail(ctx, MRCZ_EINVAL, "absolute error bound must be finite and > 0", hipSuccess);
+    uint32_t bits;
+    memcpy(&bits, &eps, 4);
+    const int32_t e = (int32_t)(bits >> 23);
+    ae->q = e ? e - 127 : -150 + (32 - __builtin_clz(bits));
+    ae->E = bits;
+    return MRCZ_OK;
+}
+
 /* byte-plane workspace of one batch: 4 planes x max_chunks x CHK bytes (as large as the batch's floats) */
 static int ensure_planes(mrcz_ctx *ctx)
 {
@@ -338,7 +351,7 @@ static int ensure_planes(mrcz_ctx *ctx)
  * offsets), phase 1 = layout in the output, phase 2 = zero + headers + emit.  The kernels index the workspace by the
  * lane-local stream number, so a lane is just a set of offset base pointers. */
 static int compress_lane(mrcz_ctx *ctx, hipStream_t lstream, int phase, int slot, uint32_t s0, const uint32_t *bin, uint64_t bfl,
-                         uint32_t nb, uint32_t mask, uint32_t fstart, uint8_t *out, int int_mode)
+                         uint32_t nb, uint32_t mask, uint32_t fstart, uint8_t *out, Xform xf, AbsErr ae)
 {
     const uint32_t ns = 4u * nb;
     TileSum *tsum = ctx->tsum + (size_t)s0 * TPS;
@@ -357,8 +370,9 @@ static int compress_lane(mrcz_ctx *ctx, hipStream_t lstream, int phase, int slot
     uint32_t *blkbase = ctx->blkbase + s0 + (uint32_t)slot; /* lane l needs 4 nb_l + 1 entries */
     uint8_t *planes = ctx->planes + (size_t)s0 * CHK;
     if (phase == 0) {
-        if (int_mode) LAUNCH("k_tile_summary", k_tile_summary<true>, dim3(SPS, nb), dim3(256), bin, bfl, mask, fstart, tsum, planes);
-        else LAUNCH("k_tile_summary", k_tile_summary<false>, dim3(SPS, nb), dim3(256), bin, bfl, mask, fstart, tsum, planes);
+        if (xf == Xform::Quant) LAUNCH("k_tile_summary", k_tile_summary<Xform::Quant>, dim3(SPS, nb), dim3(256), bin, bfl, mask, fstart, tsum, planes);
+        else if (xf == Xform::AbsErr) LAUNCH("k_tile_summary", k_tile_summary<Xform::AbsErr>, dim3(SPS, nb), dim3(256), bin, bfl, ae, fstart, tsum, planes);
+        else LAUNCH("k_tile_summary", k_tile_summary<Xform::Mask>, dim3(SPS, nb), dim3(256), bin, bfl, mask, fstart, tsum, planes);
         LAUNCH("k_stream_scan", k_stream_scan, dim3(ns), dim3(256), tsum, bfl, tinfo, sinfo, blkstart);
         /* waves per workgroup by batch size: 4 up to 12 chunks, else 1 */
         if (nb <= 12u) LAUNCH("k_histogram", k_histogram<4>, dim3(SPS, nb, 4), dim3(256), planes, bfl, tinfo, pairhist, blkstart, slideq, HIST_FEW);
@@ -386,9 +400,10 @@ static int compress_lane(mrcz_ctx *ctx, hipStream_t lstream, int phase, int slot
 }
 
 /* enqueue a compress call on the context's compute stream(s); its five result words (bytes written, per-plane sums) are copied
- * to the pinned host words h_res[0..4] in stream order.  No host synchronisation. */
+ * to the pinned host words h_res[0..4] in stream order.  No host synchronisation.  xf = what the first pass does to the words
+ * (bits applies to Xform::Mask, ae to Xform::AbsErr). */
 static int compress_enqueue(mrcz_ctx_t *ctx, const void *d_in, uint64_t nfloats, uint64_t first_chunk, int bits, void *d_out, uint64_t out_cap,
-                            uint64_t *h_res, int int_mode)
+                            uint64_t *h_res, Xform xf, AbsErr ae = AbsErr{})
 {
     if (!ctx || !d_in || !d_out || !h_res) return MRCZ_EINVAL;
     if (bits < 0 || bits > 32) return fail(ctx, MRCZ_EINVAL, "bits outside 0..32 (reference table has 33 entries, workers.c:29-37)", hipSuccess);
@@ -469,7 +484,7 @@ static int compress_enqueue(mrcz_ctx_t *ctx, const void *d_in, uint64_t nfloats,
                 }
                 const uint32_t row0 = 4u * cb; /* first workspace row (stream slot) of this lane: a chunk's rows are its place in the batch */
                 ctx->last_lc0[l] = cb; ctx->last_row0[l] = row0;
-                if (int rc = compress_lane(ctx, st, phase, (int)l, row0, in + c0 * CHK + f0, bfll, nbl, mask, fstart, out, int_mode)) return rc;
+                if (int rc = compress_lane(ctx, st, phase, (int)l, row0, in + c0 * CHK + f0, bfll, nbl, mask, fstart, out, xf, ae)) return rc;
                 if (phase == 1) {
                     HIPCHK(hipEventRecord(ctx->ev_cont, st), "event");
                     cont_pending = true;
@@ -493,7 +508,7 @@ extern "C" int mrcz_compress_chunks(mrcz_ctx_t *ctx, const void *d_in, uint64_t 
     *out_len = 0;
     if (nfloats == 0) { ctx->ntimers = 0; return (d_in && d_out) ? MRCZ_OK : MRCZ_EINVAL; }
     const double t0 = ctx->trace ? wall_now() : 0.0;
-    if (int rc = compress_enqueue(ctx, d_in, nfloats, first_chunk, bits, d_out, out_cap, ctx->h_result, 0)) return rc;
+    if (int rc = compress_enqueue(ctx, d_in, nfloats, first_chunk, bits, d_out, out_cap, ctx->h_result, Xform::Mask)) return rc;
     const double t1 = ctx->trace ? wall_now() : 0.0;
     HIPCHK(hipStreamSynchronize(ctx->stream), "stream sync (compress)");
     if (ctx->trace) fprintf(stderr, "[mrcz trace] compress %llu floats: enqueue %.1f us, wait %.1f us\n", (unsigned long long)nfloats, 1e6 * (t1 - t0), 1e6 * (wall_now() - t1));
@@ -510,7 +525,7 @@ extern "C" int mrcz_compress_chunks_int8(mrcz_ctx_t *ctx, const void *d_in, uint
     if (!ctx || !out_len) return MRCZ_EINVAL;
     *out_len = 0;
     if (nfloats == 0) { ctx->ntimers = 0; return (d_in && d_out) ? MRCZ_OK : MRCZ_EINVAL; }
-    if (int rc = compress_enqueue(ctx, d_in, nfloats, first_chunk, 0, d_out, out_cap, ctx->h_result, 1)) return rc;
+    if (int rc = compress_enqueue(ctx, d_in, nfloats, first_chunk, 0, d_out, out_cap, ctx->h_result, Xform::Quant)) return rc;
     HIPCHK(hipStreamSynchronize(ctx->stream), "stream sync (compress)");
     *out_len = ctx->h_result[0];
     if (plane_bytes)
@@ -520,13 +535,38 @@ extern "C" int mrcz_compress_chunks_int8(mrcz_ctx_t *ctx, const void *d_in, uint
 extern "C" int mrcz_compress_chunks_int8_async(mrcz_ctx_t *ctx, const void *d_in, uint64_t nfloats, uint64_t first_chunk,
                                                void *d_out, uint64_t out_cap, uint64_t *h_result5)
 {
-    return compress_enqueue(ctx, d_in, nfloats, first_chunk, 0, d_out, out_cap, h_result5, 1);
+    return compress_enqueue(ctx, d_in, nfloats, first_chunk, 0, d_out, out_cap, h_result5, Xform::Quant);
+}
+
+/* absolute-error mode: abs_round (mrcz_tile.h) replaces the mask; the records are those of -b 0 over the rounded words */
+extern "C" int mrcz_compress_chunks_abs(mrcz_ctx_t *ctx, const void *d_in, uint64_t nfloats, uint64_t first_chunk, float eps,
+                                        void *d_out, uint64_t out_cap, uint64_t *out_len, uint64_t plane_bytes[4])
+{
+    if (!ctx || !out_len) return MRCZ_EINVAL;
+    *out_len = 0;
+    AbsErr ae;
+    if (int rc = abs_err_param(ctx, eps, &ae)) return rc;
+    if (nfloats == 0) { ctx->ntimers = 0; return (d_in && d_out) ? MRCZ_OK : MRCZ_EINVAL; }
+    if (int rc = compress_enqueue(ctx, d_in, nfloats, first_chunk, 0, d_out, out_cap, ctx->h_result, Xform::AbsErr, ae)) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream), "stream sync (compress)");
+    *out_len = ctx->h_result[0];
+    if (plane_bytes)
+        for (int j = 0; j < 4; j++) plane_bytes[j] = ctx->h_result[1 + j];
+    return MRCZ_OK;
+}
+extern "C" int mrcz_compress_chunks_abs_async(mrcz_ctx_t *ctx, const void *d_in, uint64_t nfloats, uint64_t first_chunk, float eps,
+                                              void *d_out, uint64_t out_cap, uint64_t *h_result5)
+{
+    if (!ctx) return MRCZ_EINVAL;
+    AbsErr ae;
+    if (int rc = abs_err_param(ctx, eps, &ae)) return rc;
+    return compress_enqueue(ctx, d_in, nfloats, first_chunk, 0, d_out, out_cap, h_result5, Xform::AbsErr, ae);
 }
 
 extern "C" int mrcz_compress_chunks_async(mrcz_ctx_t *ctx, const void *d_in, uint64_t nfloats, uint64_t first_chunk, int bits,
                                           void *d_out, uint64_t out_cap, uint64_t *h_result5)
 {
-    return compress_enqueue(ctx, d_in, nfloats, first_chunk, bits, d_out, out_cap, h_result5, 0);
+    return compress_enqueue(ctx, d_in, nfloats, first_chunk, bits, d_out, out_cap, h_result5, Xform::Mask);
 }
 
 /* what every uncompress call checks and allocates before its first batch */
@@ -876,6 +916,20 @@ extern "C" int mrcz_erase_bits(mrcz_ctx_t *ctx, void *d_words, uint64_t nwords, 
     ctx->ntimers = 0;
     hipStream_t lstream = ctx->stream;
     LAUNCH("k_erase_bits", k_erase_bits, dim3(2048), dim3(256), (uint32_t *)d_words, nwords, first_word_index, mask_of(bits));
+    HIPCHK(hipStreamSynchronize(ctx->stream), "stream sync (erase)");
+    return MRCZ_OK;
+}
+
+extern "C" int mrcz_erase_abs(mrcz_ctx_t *ctx, void *d_words, uint64_t nwords, uint64_t first_word_index, float eps)
+{
+    if (!ctx || !d_words) return MRCZ_EINVAL;
+    AbsErr ae;
+    if (int rc = abs_err_param(ctx, eps, &ae)) return rc;
+    if (nwords == 0) return MRCZ_OK;
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->ntimers = 0;
+    hipStream_t lstream = ctx->stream;
+    LAUNCH("k_erase_abs", k_erase_abs, dim3(2048), dim3(256), (uint32_t *)d_words, nwords, first_word_index, ae);
     HIPCHK(hipStreamSynchronize(ctx->stream), "stream sync (erase)");
     return MRCZ_OK;
 }

@@ -9,7 +9,8 @@
  * Pass structure.  The first pass reads the floats once and leaves the four masked byte planes in HBM (N bytes
  * each); the two later streaming passes read a plane per wave, so the heavy planes (coded symbols) and the light
  * ones (all-zero, verbatim) are balanced by the hardware scheduler instead of idling side by side in a workgroup.
- *   k_tile_summary   4N B read, N B x 4 written : masked byte planes, per (stream, tile) run summary + interior symbol count
+ *   k_tile_summary   4N B read, N B x 4 written : masked (quantised, abs-rounded) byte planes, per (stream, tile) run summary
+ *                                              + interior symbol count
  *   k_stream_scan    small     : run extensions across tiles, symbol prefix, block count
  *   k_histogram      N B x 4 read : per (segment, block) "pair" histograms, block start positions,
  *                                window-slide positions (App. B.4)
@@ -29,9 +30,9 @@ namespace mrcz {
 /* ======================================================================================
  * pass 1: tile summaries
  * ==================================================================================== */
-template <bool QUANT>
+template <Xform X>
 __global__ __launch_bounds__(256) void k_tile_summary(const uint32_t *__restrict__ in, uint64_t nfloats,
-                                                      uint32_t mask, uint32_t first_chunk_is_file_start,
+                                                      typename XformArg<X>::type mask, uint32_t first_chunk_is_file_start,
                                                       TileSum *__restrict__ tsum, uint8_t *__restrict__ planes)
 {
     __shared__ __attribute__((aligned(16))) uint8_t lds[4 * PLANE_LDS];
@@ -48,7 +49,7 @@ __global__ __launch_bounds__(256) void k_tile_summary(const uint32_t *__restrict
         const uint32_t t0 = g * SEG + ti * TILE;
         if (t0 >= n) break;
         const int len = (int)((n - t0) < (uint32_t)TILE ? (n - t0) : (uint32_t)TILE);
-        stage_tile<QUANT>(cin, t0, (uint32_t)len, mask, unmasked, lds);
+        stage_tile<X>(cin, t0, (uint32_t)len, mask, unmasked, lds);
         __syncthreads();
         const uint8_t *plane = lds + w * PLANE_LDS;
         uint32_t x[16];

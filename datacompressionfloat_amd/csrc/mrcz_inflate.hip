@@ -13,7 +13,7 @@
  *                    parallel kernels hand over (matches with distance != 1, or malformed input)
  *   (k_merge_segments, mrcz_inflate_par.hip)  4 byte planes -> float words
  */
-#include "mrcz_common.h"
+#include "mrcz_tile.h"
 
 namespace mrcz {
 
@@ -312,6 +312,13 @@ __global__ __launch_bounds__(256) void k_erase_bits(uint32_t *__restrict__ w, ui
 {
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < nwords; i += (uint64_t)gridDim.x * 256)
         if (first_word_index + i >= 256) w[i] &= mask;
+}
+
+/* abs_round alone (mrcz_tile.h): what a container written in absolute-error mode decodes to.  In place. */
+__global__ __launch_bounds__(256) void k_erase_abs(uint32_t *__restrict__ w, uint64_t nwords, uint64_t first_word_index, AbsErr ae)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < nwords; i += (uint64_t)gridDim.x * 256)
+        if (first_word_index + i >= 256) w[i] = abs_round(w[i], ae.q, ae.E);
 }
 
 /* Synthetic volumes for the large benchmark configurations, generated where they are used: the integer generator of

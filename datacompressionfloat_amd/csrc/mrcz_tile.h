@@ -30,12 +30,47 @@ __device__ __forceinline__ uint32_t dequant_int8(uint32_t w)
     return o;
 }
 
+/* Absolute-error mode: every word becomes the float32 nearest to it (ties away from zero) whose low b mantissa bits are
+ * zero, b chosen per word as the most bits whose rounding error stays within eps, so |x - x'| <= eps for every finite x.
+ * The host passes q = floor(log2(eps)) and E = bits(eps), eps finite and > 0 (abs_err_param, mrcz_api.hip).
+ *   Inf / NaN         unchanged
+ *   |x| <= eps        +0
+ *   otherwise         u = max(e, 1) - 150 (exponent of the word's ulp), b = clamp(q - u + 1, 0, 23): the error of rounding to
+ *                     a multiple of 2^b ulps is at most 2^(b-1) ulps <= 2^q <= eps.  The carry may raise the exponent, which
+ *                     is exact (bit patterns of one sign are ordered like their values); where it would reach Inf the
+ *                     magnitude is truncated by b - 1 bits instead (error < 2^(b-1) ulps).
+ * Integer ops and selects only; the result is always finite for a finite input. */
+struct AbsErr {
+    int32_t q;
+    uint32_t E;
+};
+__device__ __forceinline__ uint32_t abs_round(uint32_t w, int32_t q, uint32_t E)
+{
+    const uint32_t e = (w >> 23) & 0xffu;
+    const uint32_t mag = w & 0x7fffffffu;
+    int32_t b = (q + 151) - (e > 1u ? (int32_t)e : 1); /* q - u + 1 */
+    b = b < 0 ? 0 : (b > 23 ? 23 : b);
+    const uint32_t half = (1u << b) >> 1;
+    uint32_t r = (mag + half) & ~((1u << b) - 1u);
+    /* r reaches 0x7f800000 (Inf) iff mag >= 0x7f800000 - half, where truncating mag by b - 1 bits gives exactly
+     * 0x7f800000 - half; every other r is at most 0x7f800000 - 2 half */
+    const uint32_t lim = 0x7f800000u - half;
+    r = r < lim ? r : lim;
+    const uint32_t o = mag <= E ? 0u : ((w & 0x80000000u) | r);
+    return e == 0xffu ? w : o;
+}
+
+/* What the first pass does to every word past the file header: the bit mask of -b, the "-s int" quantiser, or abs_round. */
+enum class Xform { Mask, Quant, AbsErr };
+template <Xform X> struct XformArg { typedef uint32_t type; }; /* Mask: the mask (Quant: unused) */
+template <> struct XformArg<Xform::AbsErr> { typedef AbsErr type; };
+
 /* All 256 threads: stage tile [t0, t0+len) of one chunk into lds[4][PLANE_LDS].
  * cin = first word of the chunk; positions below `unmasked_below` (256 for chunk 0 of a file,
  * workers.c:90-94) keep all their bits. */
-template <bool QUANT>
+template <Xform X>
 __device__ __forceinline__ void stage_tile(const uint32_t *__restrict__ cin, uint32_t t0, uint32_t len,
-                                           uint32_t mask, uint32_t unmasked_below, uint8_t *lds)
+                                           typename XformArg<X>::type mask, uint32_t unmasked_below, uint8_t *lds)
 {
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -50,11 +85,20 @@ __device__ __forceinline__ void stage_tile(const uint32_t *__restrict__ cin, uin
             if (p + 2u < len) w2 = cin[t0 + p + 2u];
         }
         const uint32_t gp = t0 + p;
-        if (QUANT) { /* "-s int": every word past the file header becomes its rounded value in one byte; no mask (workers.c:166) */
+        if constexpr (X == Xform::Quant) { /* "-s int": every word past the file header becomes its rounded value in one byte; no mask (workers.c:166) */
             if (gp >= unmasked_below) w0 = quant_int8(w0);
             if (gp + 1u >= unmasked_below) w1 = quant_int8(w1);
             if (gp + 2u >= unmasked_below) w2 = quant_int8(w2);
             if (gp + 3u >= unmasked_below) w3 = quant_int8(w3);
+        } else if constexpr (X == Xform::AbsErr) { /* as the mask: the file header keeps its bits; padding words stay 0 */
+            if (gp >= unmasked_below) {
+                w0 = abs_round(w0, mask.q, mask.E); w1 = abs_round(w1, mask.q, mask.E);
+                w2 = abs_round(w2, mask.q, mask.E); w3 = abs_round(w3, mask.q, mask.E);
+            } else {
+                if (gp + 1u >= unmasked_below) w1 = abs_round(w1, mask.q, mask.E);
+                if (gp + 2u >= unmasked_below) w2 = abs_round(w2, mask.q, mask.E);
+                if (gp + 3u >= unmasked_below) w3 = abs_round(w3, mask.q, mask.E);
+            }
         } else if (gp >= unmasked_below) {
             w0 &= mask; w1 &= mask; w2 &= mask; w3 &= mask;
         } else {

@@ -5,13 +5,31 @@
  * compared with this tool's output in the reference's round-trip test (run_full_test.sh:84-102).  Trailing
  * bytes that do not fill a 32-bit word are dropped, as the reference's fread(…, sizeof(float), …) does.  One
  * divergence: for a file shorter than 1024 bytes the reference writes 1024 bytes of its (uninitialised) buffer
- * (erasebytes.c:105-107); this tool writes the bytes it read.
+ * (erasebytes.c:105-107); this tool writes the bytes it read.  Extension: -e <eps> writes what a container of
+ * `mrc_tar -e <eps>` decodes to (mrcz_erase_abs) instead of masking.
  */
 #include "../../include/mrcz_hip.h"
 
+#include <float.h>
 #include <getopt.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
+
+/* the bound as mrcz_workers_set_abs_error takes it: float32 toward zero (0 for anything it refuses) */
+static float abs_bound(double eps)
+{
+    if (!(eps > 0.0) || !isfinite(eps)) return 0.0f;
+    float f = eps > FLT_MAX ? FLT_MAX : (float)eps;
+    if ((double)f > eps) {
+        uint32_t u;
+        memcpy(&u, &f, 4);
+        u--;
+        memcpy(&f, &u, 4);
+    }
+    return f;
+}
 
 static void usage(char **argv)
 {
@@ -19,18 +37,22 @@ static void usage(char **argv)
     printf("\t-i\tinput file that need to erase lowest byte\n\n");
     printf("\t-o\t output file that save the float number with lowerest byte to be \\0\n\n");
     printf("\t-b\t bits to be erased, default is 8\n\n");
+    printf("\t-e\t absolute error bound instead of -b: the words a container of mrc_tar -e <eps> decodes to (extension of the MI355X build)\n\n");
 }
 
 int main(int argc, char *argv[])
 {
     const char *in = NULL, *out = NULL;
-    int bits = 8, opt;
+    const char *eps_arg = NULL;
+    int bits = 8, bits_given = 0, opt;
+    float eps = 0.0f;
     if (argc < 2) { usage(argv); exit(-1); }
-    while ((opt = getopt(argc, argv, "hi:o:b:")) != -1) {
+    while ((opt = getopt(argc, argv, "hi:o:b:e:")) != -1) {
         switch (opt) {
         case 'i': in = optarg; break;
         case 'o': out = optarg; break;
-        case 'b': bits = atoi(optarg); break;
+        case 'b': bits = atoi(optarg); bits_given = 1; break;
+        case 'e': eps_arg = optarg; break;
         case 'h': usage(argv); return 0;
         default: printf("Invalid command line parameters!\n"); usage(argv); return -1;
         }
@@ -40,7 +62,18 @@ int main(int argc, char *argv[])
         fprintf(stderr, "[%s:%d] bits to erase must be in 0..32\n", __FILE__, __LINE__);
         exit(-1);
     }
-    printf("Input File = %s, Output File = %s, bitsToErase = %d\n", in, out, bits);
+    if (eps_arg) {
+        char *end;
+        const double e = strtod(eps_arg, &end);
+        eps = (end == eps_arg || *end) ? 0.0f : abs_bound(e);
+        if (!(eps > 0.0f) || bits_given) {
+            fprintf(stderr, "[%s:%d] -e needs a finite bound > 0 and excludes -b\n", __FILE__, __LINE__);
+            exit(-1);
+        }
+        printf("Input File = %s, Output File = %s, absErrorBound = %.9g\n", in, out, (double)eps);
+    } else {
+        printf("Input File = %s, Output File = %s, bitsToErase = %d\n", in, out, bits);
+    }
     FILE *fi = fopen(in, "rb"), *fo = fopen(out, "wb");
     if (!fi) { fprintf(stderr, "[%s:%d] open file [%s] failed\n", __FILE__, __LINE__, in); exit(-1); }
     if (!fo) { fprintf(stderr, "[%s:%d] open file [%s] failed\n", __FILE__, __LINE__, out); exit(-1); }
@@ -55,7 +88,8 @@ int main(int argc, char *argv[])
     uint64_t word0 = 256; /* index, inside the file, of the first word of the next block */
     size_t num;
     while ((num = fread(h, 4, (size_t)ITEMS, fi)) > 0) {
-        if (mrcz_copy_h2d(c, d, h, (uint64_t)num * 4) || mrcz_erase_bits(c, d, (uint64_t)num, word0, bits) ||
+        if (mrcz_copy_h2d(c, d, h, (uint64_t)num * 4) ||
+            (eps_arg ? mrcz_erase_abs(c, d, (uint64_t)num, word0, eps) : mrcz_erase_bits(c, d, (uint64_t)num, word0, bits)) ||
             mrcz_copy_d2h(c, h, d, (uint64_t)num * 4)) {
             fprintf(stderr, "[%s:%d] GPU step failed: %s\n", __FILE__, __LINE__, mrcz_last_error(c));
             exit(-1);

@@ -1,7 +1,8 @@
 /*
  * mrc_tar.c -- single-file front-end with the reference's command line
  * (/root/reference/src/main/mrc_tar.c:82-165): mrc_tar -i <in> -o <out> [-t zip|unzip] [-b 0..32]
- * [-s float|int] [-h].  The work is done by run_compress / run_uncompress on the GPU.
+ * [-s float|int] [-h].  The work is done by run_compress / run_uncompress on the GPU.  Extension: -e <eps>, the
+ * absolute-error mode of the compressor (mrcz_workers_set_abs_error); unzip needs nothing for it.
  */
 #include "../../include/mrcz_hip.h"
 #include "../../include/mrcz_workers.h"
@@ -18,6 +19,7 @@ static void usage(char **argv) /* mrc_tar.c:82-100 */
     printf("\t-b\t bits to be erased, range[0..32], default is 0\n\n");
     printf("\t-s\t data type to be converted to when compressed/decompressed, value should be [float | int], default is float\n\n");
     printf("\t-t\t operation type, e.g compress or decompressed file, value should be [zip | unzip], default is zip\n\n");
+    printf("\t-e\t absolute error bound: every decoded float within eps of the original, eps > 0 (zip only; excludes -b and -s int) (extension of the MI355X build)\n\n");
     printf("\t-g\t first HIP device to use, default 0 (extension of the MI355X build)\n\n");
     printf("\t-G\t number of HIP devices the file's chunks are dealt to, default 1; 0 = all visible devices (extension of the MI355X build)\n\n");
 }
@@ -33,9 +35,10 @@ int main(int argc, char *argv[])
 {
     const double t_main = wall_now();
     const char *in = NULL, *out = NULL, *op = "zip", *dtype = "float";
+    const char *eps = NULL;
     int bits = 0, opt, dev0 = 0, ndev = 1;
     if (argc < 2) { usage(argv); exit(-1); }
-    while ((opt = getopt(argc, argv, "hi:o:b:t:s:g:G:")) != -1) {
+    while ((opt = getopt(argc, argv, "hi:o:b:t:s:g:G:e:")) != -1) {
         switch (opt) {
         case 'i': in = optarg; break;
         case 'o': out = optarg; break;
@@ -44,11 +47,21 @@ int main(int argc, char *argv[])
         case 's': dtype = optarg; break;
         case 'g': dev0 = atoi(optarg); break;
         case 'G': ndev = atoi(optarg); break;
+        case 'e': eps = optarg; break;
         case 'h': usage(argv); return 0;
         default: printf("Invalid command line parameters!\n"); usage(argv); return -1;
         }
     }
     if (!in || !out) { usage(argv); return -1; }
+    if (eps && strcmp(op, "zip") == 0) {
+        char *end;
+        const double e = strtod(eps, &end);
+        if (end == eps || *end || bits != 0 || strcmp(dtype, "int") == 0 || e == 0.0 || mrcz_workers_set_abs_error(e) != 0) {
+            printf("Invalid command line parameters: -e needs a finite bound > 0 and excludes -b and -s int\n");
+            usage(argv);
+            return -1;
+        }
+    }
     if (ndev != 1) {
         /* -G n: the file's chunks are dealt over n GPUs of the node, -G 0 over all of them.  Opt-in: every extra
          * device costs an engine (workspace, streams, batch buffers) inside the timed call, which one file has to be large to

@@ -4,7 +4,8 @@
  * [-b bits] [-n threads=2] [-d 0|1] [-s ...] [-h].  N worker threads pull whole files from the
  * mutex-protected list (mrc_tarx.c:41-176); every worker owns one GPU codec context and workers are
  * dealt round-robin over the visible MI355X devices, so "-n 8" on an 8-GPU node runs one file per GPU
- * at a time with pinned-buffer I/O overlapped inside run_compress.
+ * at a time with pinned-buffer I/O overlapped inside run_compress.  Extension: -e <eps>, the absolute-error mode of the
+ * compressor for every file (mrcz_workers_set_abs_error).
  */
 #include "../../include/mrcz_hip.h"
 #include "../../include/mrcz_workers.h"
@@ -49,14 +50,15 @@ static void usage(char **argv) /* mrc_tarx.c:322-343 */
     printf("\t-d\t whether to test the throughput, range[0 | 1 ], default is 0 means not to test throughput, 1 means to test the throughput\n\n");
     printf("\t-t\t operation type, e.g compress or decompressed file, value should be [zip | unzip]\n\n");
     printf("\t-n\t thread numbers, default is 2\n\n");
+    printf("\t-e\t absolute error bound: every decoded float within eps of the original, eps > 0 (zip only; excludes -b and -s int) (extension of the MI355X build)\n\n");
 }
 
 int main(int argc, char *argv[])
 {
-    const char *list = NULL, *outdir = "/tmp/", *op = NULL;
+    const char *list = NULL, *outdir = "/tmp/", *op = NULL, *eps = NULL, *dtype = "float";
     int bits = 0, threads = 2, opt;
     if (argc < 2) { usage(argv); exit(-1); }
-    while ((opt = getopt(argc, argv, "hi:o:b:t:n:d:s:")) != -1) {
+    while ((opt = getopt(argc, argv, "hi:o:b:t:n:d:s:e:")) != -1) {
         switch (opt) {
         case 'i': list = optarg; break;
         case 'o': outdir = optarg; break;
@@ -64,7 +66,8 @@ int main(int argc, char *argv[])
         case 't': op = optarg; break;
         case 'n': threads = atoi(optarg); break;
         case 'd': isTestThroughput = atoi(optarg); break; /* mrc_tarx.c:386 */
-        case 's': break;                                  /* parsed and ignored, as in the reference (mrc_tarx.c:393-394) */
+        case 's': dtype = optarg; break;                  /* ignored, as in the reference (mrc_tarx.c:393-394), but for the -e check */
+        case 'e': eps = optarg; break;
         case 'h': usage(argv); return 0;
         default: printf("Invalid command line parameters!\n"); usage(argv); return -1;
         }
@@ -72,6 +75,15 @@ int main(int argc, char *argv[])
     if (!list || !op || threads < 1) { usage(argv); return -1; }
     const int unzip = strcmp(op, "unzip") == 0;
     if (!unzip && strcmp(op, "zip") != 0) { usage(argv); return -1; }
+    if (eps && !unzip) {
+        char *end;
+        const double e = strtod(eps, &end);
+        if (end == eps || *end || bits != 0 || strcmp(dtype, "int") == 0 || e == 0.0 || mrcz_workers_set_abs_error(e) != 0) {
+            printf("Invalid command line parameters: -e needs a finite bound > 0 and excludes -b and -s int\n");
+            usage(argv);
+            return -1;
+        }
+    }
     file_container_t fnames;
     init_file_container_ex(&fnames, list, outdir, (char *)op);
     print_file_container_info(&fnames);

@@ -25,6 +25,8 @@
 #include "../../include/mrcz_hip.h"
 #include "../../include/mrcz_workers.h"
 
+#include <float.h>
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include <sys/mman.h>
@@ -45,6 +47,7 @@ static __thread int t_device = 0; /* first (logical) device of the calling threa
 static __thread int t_ndev = 1;   /* devices the thread's calls deal their batches to: t_device .. t_device + t_ndev - 1 */
 static int g_pipes_active = 0; /* pipelines (files) in flight in this process: their helper threads share the host's cores */
 static int g_batch_chunks = 8; /* chunks per device batch: 192 MiB of floats */
+static float g_abs_eps = 0.0f; /* absolute-error bound of run_compress; 0 = off (the mask of bitsToMask) */
 
 void mrcz_workers_set_device(int device) { t_device = device; t_ndev = 1; }
 /* the chunks of ONE file dealt over several GPUs.  Batch k of a call goes to device first + k % ndevices; every
@@ -55,6 +58,21 @@ void mrcz_workers_set_devices(int first, int ndevices)
     t_ndev = ndevices < 1 ? 1 : (ndevices > MAXND ? MAXND : ndevices);
 }
 void mrcz_workers_set_batch_chunks(int chunks) { g_batch_chunks = chunks < 1 ? 1 : (chunks > 128 ? 128 : chunks); }
+int mrcz_workers_set_abs_error(double eps)
+{
+    if (eps == 0.0) { g_abs_eps = 0.0f; return 0; }
+    if (!(eps > 0.0) || !isfinite(eps)) return -1;
+    float f = eps > FLT_MAX ? FLT_MAX : (float)eps;
+    if ((double)f > eps) { /* rounded up: one step toward zero, so that the bound holds for the value given */
+        uint32_t u;
+        memcpy(&u, &f, 4);
+        u--;
+        memcpy(&f, &u, 4);
+    }
+    if (!(f > 0.0f)) return -1; /* below the smallest float32 */
+    g_abs_eps = f;
+    return 0;
+}
 static int batch_chunks(void) /* MRCZ_BATCH_CHUNKS overrides the default (tests: several batches from small files) */
 {
     const char *e = getenv("MRCZ_BATCH_CHUNKS");
@@ -282,6 +300,7 @@ typedef struct {
     FILE *fin, *fout;
     int decode;           /* 0 = run_compress, 1 = run_uncompress */
     int int_mode;         /* dataConvertedType == "int" (workers.c:782-787, 604-609) */
+    float abs_eps;        /* compress: absolute-error bound (mrcz_workers_set_abs_error), 0 = off */
     signed char ztypes[4];/* decode: compressor types of the four byte streams (file header) */
     int bits;
     uint32_t chk;         /* floats per chunk */
@@ -691,7 +710,9 @@ static void run_pipeline(pipe_t *p)
         pthread_mutex_lock(&D->e->mu);
         CK(mrcz_stream_wait_event(c, MRCZ_STREAM_COMPUTE, D->up_ev[b]), "stream wait", c);
         if (k >= inflight) CK(mrcz_stream_wait_event(c, MRCZ_STREAM_COMPUTE, D->down_ev[b]), "stream wait", c);
-        if (!p->decode && !p->int_mode)
+        if (!p->decode && p->abs_eps > 0.0f)
+            CK(mrcz_compress_chunks_abs_async(c, D->d_a[b], bt.units, bt.first_chunk, p->abs_eps, D->d_b[b], rec_cap, D->h_res[b]), "compress", c);
+        else if (!p->decode && !p->int_mode)
             CK(mrcz_compress_chunks_async(c, D->d_a[b], bt.units, bt.first_chunk, p->bits, D->d_b[b], rec_cap, D->h_res[b]), "compress", c);
         else if (!p->decode)
             CK(mrcz_compress_chunks_int8_async(c, D->d_a[b], bt.units, bt.first_chunk, D->d_b[b], rec_cap, D->h_res[b]), "compress", c);
@@ -751,6 +772,11 @@ int run_compress(FILE *fin, ctx_t *ctx, FILE *fout, const int bitsToMask, const 
         fprintf(stderr, "[%s:%d] ERROR: bits to erase must be in 0..32 (table of 33 masks, workers.c:29-37)\n", __FILE__, __LINE__);
         mrcz_workers_fatal_exit();
     }
+    const float abs_eps = g_abs_eps;
+    if (abs_eps > 0.0f && (bitsToMask != 0 || int_mode)) {
+        fprintf(stderr, "[%s:%d] ERROR: an absolute-error bound excludes bits to erase and the int mode\n", __FILE__, __LINE__);
+        mrcz_workers_fatal_exit();
+    }
     const double begin = now_sec();
     const uint64_t fsz = get_file_size(fin);
     const uint64_t file_floats = fsz / 4u;
@@ -764,7 +790,8 @@ int run_compress(FILE *fin, ctx_t *ctx, FILE *fout, const int bitsToMask, const 
 
     pipe_t p;
     memset(&p, 0, sizeof(p));
-    p.fin = fin; p.fout = fout; p.decode = 0; p.int_mode = int_mode; p.bits = bitsToMask; p.chk = CHUNK_SIZE; p.total_floats = file_floats;
+    p.fin = fin; p.fout = fout; p.decode = 0; p.int_mode = int_mode; p.abs_eps = abs_eps; p.bits = bitsToMask; p.chk = CHUNK_SIZE;
+    p.total_floats = file_floats;
     const double elapsed = run_file(&p, begin, "run_compress");
     ctx->zipTime += elapsed;
     /* workers.c:863-873: the per-plane table, then the sum of the per-plane compressed sizes (each includes its 4-byte header) */

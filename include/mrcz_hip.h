@@ -150,6 +150,28 @@ int mrcz_uncompress_chunks_int8_async(mrcz_ctx_t *ctx, const void *d_records, ui
                                       uint64_t first_chunk, void *d_out, uint64_t *h_result3);
 
 /*
+ * Absolute-error mode: every decoded float lies within eps of the original (|x - x'| <= eps in exact arithmetic), with as
+ * many low bits zeroed per word as that bound allows.  eps is a float32, finite and > 0 (else MRCZ_EINVAL); a caller that
+ * holds a double converts it toward zero, so that the bound also holds for the value it was given.  With
+ * q = floor(log2(eps)) and E = bits(eps), every word w past the file's first 256 (as -b treats them) becomes:
+ *   e = (w >> 23) & 0xff == 0xff (Inf, NaN)   w
+ *   mag = w & 0x7fffffff <= E (|x| <= eps)    0 (+0.0)
+ *   otherwise                                 b = clamp(q - (max(e, 1) - 150) + 1, 0, 23);
+ *                                             r = (mag + (b ? 1 << (b - 1) : 0)) & ~((1 << b) - 1)   (nearest, ties away from 0)
+ *                                             r >= 0x7f800000 (would round to Inf): r = mag & ~((1 << (b - 1)) - 1);
+ *                                             (w & 0x80000000) | r
+ * then the same plane split / DEFLATE / container as bits = 0.  Nothing is recorded in the container and nothing is needed
+ * to decode it: every decoder (mrcz_uncompress_chunks, range, boxes, binned, the reference's reader) returns the rounded
+ * words.  mrcz_erase_abs applies the same rounding in place to words [256, nwords) of a file (d_words holds words
+ * first_word_index ..): the expected decode, as mrcz_erase_bits is for bits.
+ */
+int mrcz_compress_chunks_abs(mrcz_ctx_t *ctx, const void *d_in, uint64_t nfloats, uint64_t first_chunk, float eps,
+                             void *d_out, uint64_t out_cap, uint64_t *out_len, uint64_t plane_bytes[4]);
+int mrcz_compress_chunks_abs_async(mrcz_ctx_t *ctx, const void *d_in, uint64_t nfloats, uint64_t first_chunk, float eps,
+                                   void *d_out, uint64_t out_cap, uint64_t *h_result5);
+int mrcz_erase_abs(mrcz_ctx_t *ctx, void *d_words, uint64_t nwords, uint64_t first_word_index, float eps);
+
+/*
  * Range decode: words [w0, w1) of a file without decoding the rest.  Nothing in the container changes: every chunk record
  * starts with a 16-byte header holding its four payload lengths, so where chunk c's record begins follows from the headers
  * of chunks 0 .. c-1 alone, and the chunks decode independently.  Only the chunks that cover the window are decoded (whole),

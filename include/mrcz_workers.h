@@ -69,6 +69,11 @@ void mrcz_workers_set_device(int device);
  * every device codes its chunk ranges independently and the records are written in file order.  Thread-local, like set_device. */
 void mrcz_workers_set_devices(int first, int ndevices);
 void mrcz_workers_set_batch_chunks(int chunks);
+/* Absolute-error mode of run_compress for the whole process (include/mrcz_hip.h, mrcz_compress_chunks_abs): every decoded float
+ * within eps of the original.  eps is converted to float32 toward zero; 0 = off (the default: the mask of bitsToMask).  Returns 0,
+ * or -1 (setting unchanged) for eps < 0, NaN, Inf or a bound below the smallest float32.  run_compress reads it when it starts and
+ * fails, as for a bad bitsToMask, when it is on together with bitsToMask != 0 or the int mode.  Decoding needs nothing. */
+int mrcz_workers_set_abs_error(double eps);
 /* What the library's own fatal errors leave through (the reference's exit(-1), src/core/workers.c:708-712, adapt.c:34-44): stdio
  * flushed, then _exit(255) -- the errors are raised by pipeline or worker threads while others still use the GPU, and exit
  * handlers run under them crash instead of exiting. */
