@@ -23,6 +23,14 @@ class MrczBinGeom(ctypes.Structure):
                 ("fx", ctypes.c_uint32), ("fy", ctypes.c_uint32), ("fz", ctypes.c_uint32)]
 
 
+class MrczCompare(ctypes.Structure):
+    """mrcz_compare_t: the error summary of one chunk, or of a whole file, against the original"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("n", "n_header_diff", "n_diff", "n_finite", "n_special_diff", "n_over_abs", "n_over_rel",
+                                               "first_over", "max_err_index", "max_rel_index")] + \
+               [(k, ctypes.c_double) for k in ("max_err", "max_rel", "sum_err", "sum_abs_err", "sum_err2", "orig_min", "orig_max",
+                                               "orig_sum", "orig_sum2")]
+
+
 def load():
     if not os.path.exists(LIB_PATH):
         raise MrczLibraryMissing(
@@ -71,6 +79,10 @@ def load():
     lib.mrcz_uncompress_binned.argtypes = [vp, vp, u64, u64, u32, u64, u64, bgeom, vp, i32, ctypes.POINTER(u64)]
     lib.mrcz_binned_finish.restype = i32
     lib.mrcz_binned_finish.argtypes = [vp, bgeom, vp, vp]
+    lib.mrcz_uncompress_compare.restype = i32
+    lib.mrcz_uncompress_compare.argtypes = [vp, vp, u64, u64, u32, u64, u64, vp, ctypes.c_double, ctypes.c_double, i32, vp]
+    lib.mrcz_compare_finish.restype = i32
+    lib.mrcz_compare_finish.argtypes = [vp, vp, u64, u64, ctypes.POINTER(MrczCompare)]
     lib.mrcz_generate_kat_words.restype = i32
     lib.mrcz_generate_kat_words.argtypes = [vp, vp, u64, u64]
     lib.mrcz_set_ztypes.restype = i32
@@ -103,4 +115,5 @@ EXPORTS = [
     "mrcz_box_origins", "mrcz_boxes_chunks", "mrcz_uncompress_boxes",
     "mrcz_bin_chunks", "mrcz_uncompress_binned", "mrcz_binned_finish",
     "mrcz_compress_chunks_abs", "mrcz_compress_chunks_abs_async", "mrcz_erase_abs",
+    "mrcz_uncompress_compare", "mrcz_compare_finish",
 ]

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MrczBinGeom, MrczBoxGeom
+from ._lib import MrczBinGeom, MrczBoxGeom, MrczCompare
 
 CHUNK_FLOATS = 6 * 1048576  # src/include/constant.h:25
 FILE_HEADER_BYTES = 17      # src/core/common.c:137-148
@@ -236,6 +236,108 @@ class MrcZipCodec:
         if rc != 0:
             raise self._err("mrcz_binned_finish", rc)
         return out
+
+    def uncompress_compare_device(self, records: torch.Tensor, nfloats_file: int, orig: torch.Tensor, acc: torch.Tensor, first_chunk: int = 0,
+                                  nchunks: int = None, abs_err=None, rel_err=None, chk: int = CHUNK_FLOATS, int_mode: bool = False):
+        """compare decode, one step (mrcz_uncompress_compare): `records` (cuda uint8) = the chunk records of chunks [first_chunk,
+        first_chunk + nchunks) of a file of nfloats_file floats (default: every chunk from first_chunk on); `orig` (cuda, 4-byte
+        elements) = the original's words of exactly those chunks.  Assigns chunk c's summary to record c of `acc`, a cuda uint8
+        tensor of ceil(nfloats_file / chk) * sizeof(MrczCompare) bytes (no zeroing needed).  abs_err / rel_err: the bounds
+        counted in n_over_abs / n_over_rel (None: off).  Steps cover the chunks in any order, each once; then
+        compare_finish_device."""
+        assert records.is_cuda and records.dtype == torch.uint8 and records.is_contiguous()
+        if nchunks is None:
+            nchunks = max((nfloats_file + chk - 1) // chk - first_chunk, 0)
+        nwords = max(min(nchunks * chk, nfloats_file - first_chunk * chk), 0)
+        assert orig.is_cuda and orig.is_contiguous() and orig.element_size() == 4 and orig.numel() >= nwords
+        nch = (nfloats_file + chk - 1) // chk
+        assert acc.is_cuda and acc.dtype == torch.uint8 and acc.is_contiguous() and acc.numel() >= nch * ctypes.sizeof(MrczCompare)
+        torch.cuda.current_stream(records.device).synchronize()
+        rc = _LIB.mrcz_uncompress_compare(self._ctx, records.data_ptr(), records.numel(), nfloats_file, chk, first_chunk, nchunks,
+                                          orig.data_ptr(), -1.0 if abs_err is None else float(abs_err),
+                                          -1.0 if rel_err is None else float(rel_err), 1 if int_mode else 0, acc.data_ptr())
+        if rc != 0:
+            raise self._err("mrcz_uncompress_compare", rc)
+
+    def compare_finish_device(self, acc: torch.Tensor, first_chunk: int, nchunks: int) -> MrczCompare:
+        """the fold of chunk records [first_chunk, first_chunk + nchunks) of `acc` (mrcz_compare_finish) as an MrczCompare"""
+        assert acc.is_cuda and acc.dtype == torch.uint8 and acc.numel() >= (first_chunk + nchunks) * ctypes.sizeof(MrczCompare)
+        total = MrczCompare()
+        rc = _LIB.mrcz_compare_finish(self._ctx, acc.data_ptr(), first_chunk, nchunks, ctypes.byref(total))
+        if rc != 0:
+            raise self._err("mrcz_compare_finish", rc)
+        return total
+
+    @staticmethod
+    def _compare_dict(rec: MrczCompare) -> dict:
+        return {k: getattr(rec, k) for k, _ in MrczCompare._fields_}
+
+    def verify(self, container_or_path, original, abs_err=None, rel_err=None, mode: str = "float", per_chunk: bool = False):
+        """how well a container reproduces `original` (bytes, a path, or a cuda tensor of the file's words), without holding the
+        decoded volume: the container's records are read and compared in pieces of at most max_batch_chunks chunks, a host
+        original is uploaded in the same pieces.  Returns the file's MrczCompare fields as a dict with the derived mean_err,
+        rmse, psnr_db (inf when rmse == 0) and ok: no header word differs and, if a bound was given, no point exceeds it and no
+        NaN / Inf word differs (the verdict of mrc_verify).  per_chunk: (dict, list of the chunks' dicts)."""
+        if mode not in ("float", "int"):
+            raise MrczError("mode must be 'float' or 'int' (mrc_tar -s)")
+        with self._open(container_or_path) as f:
+            nfl, chk = self._container_header(f)
+            f.seek(0)
+            fsz = unpack_file_header(f.read(FILE_HEADER_BYTES))[0]
+            dev = isinstance(original, torch.Tensor)
+            if dev:
+                assert original.is_cuda and original.is_contiguous() and original.element_size() == 4
+                osz = original.numel() * 4
+                src = None
+            else:
+                src = io.BytesIO(original) if isinstance(original, (bytes, bytearray, memoryview)) else open(original, "rb")
+                osz = src.seek(0, os.SEEK_END)
+            try:
+                if osz != fsz and not (dev and osz == nfl * 4):
+                    raise MrczError(f"the original holds {osz} bytes, the container records {fsz}")
+                nch = (nfl + chk - 1) // chk
+                offs, off, size_ = [], FILE_HEADER_BYTES, ctypes.c_uint64()
+                for c in range(nch):
+                    offs.append(off)
+                    f.seek(off)
+                    h = f.read(16)
+                    if len(h) < 16 or _LIB.mrcz_record_size(h, min(chk, nfl - c * chk), ctypes.byref(size_)) != 0:
+                        raise MrczError(f"damaged or truncated container: chunk header {c} at byte {off}")
+                    off += size_.value
+                offs.append(off)
+                rsz = ctypes.sizeof(MrczCompare)
+                acc = torch.empty(max(nch, 1) * rsz, dtype=torch.uint8, device=self.device)
+                step = max(int(self.max_batch_chunks), 1)
+                for k in range(0, nch, step):
+                    e = min(k + step, nch)
+                    f.seek(offs[k])
+                    body = f.read(offs[e] - offs[k])
+                    if len(body) != offs[e] - offs[k]:
+                        raise MrczError("truncated container: the records end early")
+                    rec = torch.frombuffer(bytearray(body), dtype=torch.uint8).to(self.device)
+                    w0, w1 = k * chk, min(e * chk, nfl)
+                    if dev:
+                        org = original.reshape(-1)[w0:w1]
+                    else:
+                        src.seek(4 * w0)
+                        org = torch.frombuffer(bytearray(src.read(4 * (w1 - w0))), dtype=torch.int32).to(self.device)
+                    self.uncompress_compare_device(rec, nfl, org, acc, first_chunk=k, nchunks=e - k, abs_err=abs_err, rel_err=rel_err, chk=chk,
+                                                   int_mode=(mode == "int"))
+                    del rec, org
+                t = self._compare_dict(self.compare_finish_device(acc, 0, nch))
+            finally:
+                if src is not None:
+                    src.close()
+        n = t["n_finite"]
+        t["mean_err"] = t["sum_err"] / n if n else 0.0
+        t["rmse"] = float(np.sqrt(t["sum_err2"] / n)) if n else 0.0
+        t["psnr_db"] = float("inf") if t["rmse"] == 0 else float(20.0 * np.log10((t["orig_max"] - t["orig_min"]) / t["rmse"]))
+        bounded = abs_err is not None or rel_err is not None
+        t["ok"] = t["n_header_diff"] == 0 and (not bounded or (t["n_over_abs"] == 0 and t["n_over_rel"] == 0 and t["n_special_diff"] == 0))
+        if not per_chunk:
+            return t
+        raw = acc.cpu().numpy().tobytes()
+        return t, [self._compare_dict(MrczCompare.from_buffer_copy(raw[c * rsz: (c + 1) * rsz])) for c in range(nch)]
 
     def erase_bits_device(self, words: torch.Tensor, bits: int, first_word_index: int = 0):
         assert words.is_cuda and words.element_size() == 4

@@ -40,6 +40,8 @@ constexpr uint32_t BLK_WGS_PER_CU = 3;
  * overlap (1 GiB: 2048 waves 279 us, 8192 159, 32768 128) */
 static uint32_t validate_grid(uint32_t ns) { return ns * 192u < 4096u ? 4096u : ns * 192u > 32768u ? 32768u : ns * 192u; }
 
+namespace mrcz { struct CmpPart; } /* mrcz_compare.hip */
+
 struct mrcz_ctx {
     int device;
     uint32_t max_chunks;
@@ -91,6 +93,7 @@ struct mrcz_ctx {
     unsigned long long *errhist; /* erroranalysis: 2048 histogram bins + the candidate counter; allocated on first use */
     uint8_t *planes;       /* byte planes of one batch (stream s at s * CHK), both directions; allocated on first use */
     uint32_t *stage;       /* box and binned decode: the words of one batch (max_chunks x CHK); allocated on first use */
+    CmpPart *cmp_part;     /* compare decode: CMP_WGS partial summaries per chunk of a batch; allocated on first use */
     uint32_t *boxbuf;      /* box decode: origins and box lists of a call (boxbuf_words words) */
     uint64_t boxbuf_words;
     /* timing */
@@ -238,6 +241,7 @@ extern "C" void mrcz_destroy(mrcz_ctx_t *ctx)
     (void)hipFree(ctx->dbgphase);
     (void)hipFree(ctx->planes);
     (void)hipFree(ctx->stage);
+    (void)hipFree(ctx->cmp_part);
     (void)hipFree(ctx->boxbuf);
     (void)hipFree(ctx->errhist);
     if (ctx->h_result) (void)hipHostFree(ctx->h_result);
@@ -795,6 +799,9 @@ extern "C" int mrcz_uncompress_range_async(mrcz_ctx_t *ctx, const void *d_record
 
 /* ---- binned decode: an average-pooled float32 volume, the chunks streamed through the staging buffer ---- */
 #include "mrcz_binned.hip"
+
+/* ---- compare decode: an error summary per chunk against the original's words, through the same staging buffer ---- */
+#include "mrcz_compare.hip"
 
 /* ---- events and the three streams of a context (pipelines: include/mrcz_hip.h) ---- */
 struct mrcz_event { hipEvent_t ev; };

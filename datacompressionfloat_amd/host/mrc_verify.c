@@ -1,0 +1,196 @@
+/*
+ * mrc_verify.c -- compare decode from the command line: is the original reproduced by its container, and how well?
+ *
+ *   mrc_verify -a vol.mrc -z vol.mrc.zip [-e eps] [-r rel] [-s float|int] [-c] [-g device]
+ *
+ *   -a   the original file
+ *   -z   the container written from it by mrc_tar -t zip
+ *   -e   absolute bound: the verdict fails if a finite point has |decoded - original| > eps (mrc_tar -e promises <= eps)
+ *   -r   relative bound: the verdict fails if a finite point with |original| > 1e-3 has |decoded - original| / |original| > rel
+ *   -s   decode mode, as mrc_tar -s (the container does not record it)
+ *   -c   one line per chunk as well: "chunk c max_err rmse n_diff", the error profile along the file
+ *
+ * The container is decoded on the device in runs of the context's batch (16 chunks); the original passes through a pinned buffer
+ * in the same runs, one mrcz_uncompress_compare per run, one mrcz_compare_finish.  The decoded words are never written anywhere.
+ * Prints one "key value" line per field of mrcz_compare_t (include/mrcz_hip.h) and the derived mean_err = sum_err / n_finite,
+ * rmse = sqrt(sum_err2 / n_finite), psnr_db = 20 log10((orig_max - orig_min) / rmse).
+ * Exit status: 0 when no header word differs and, if a bound was given, no point exceeds it and no NaN / Inf word differs; 1 when
+ * that verdict fails; 255 for bad arguments, unreadable files and malformed containers.
+ */
+#include "../../include/mrcz_hip.h"
+
+#include <errno.h>
+#include <fcntl.h>
+#include <inttypes.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#define BATCH 16u
+
+static void usage(const char *prog)
+{
+    printf("\nUsage:\n\n\t%s -a <original> -z <container> [-e <eps>] [-r <rel>] [-s float|int] [-c] [-g device]\nwhere:\n", prog);
+    printf("\t-a\tthe original file\n\n");
+    printf("\t-z\tcontainer written from it by mrc_tar -t zip\n\n");
+    printf("\t-e\tabsolute error bound of the verdict\n\n");
+    printf("\t-r\trelative error bound of the verdict\n\n");
+    printf("\t-s\tdata type the container was written with, [float | int], default float\n\n");
+    printf("\t-c\tprint the error of every chunk as well\n\n");
+    printf("\t-g\tHIP device, default 0\n\n");
+}
+
+/* errors leave with the reference's exit(-1) status (255), never through a signal (as mrc_extract) */
+static void die(const char *what, mrcz_ctx_t *c)
+{
+    fprintf(stderr, "[%s:%d] ERROR: %s%s%s\n", __FILE__, __LINE__, what, c ? ": " : "", c ? mrcz_last_error(c) : "");
+    fflush(stdout);
+    fflush(stderr);
+    _exit(255);
+}
+
+static void pread_all(int fd, void *buf, uint64_t n, uint64_t off, const char *what)
+{
+    uint8_t *p = (uint8_t *)buf;
+    while (n) {
+        const ssize_t r = pread(fd, p, n > (1u << 30) ? (1u << 30) : (size_t)n, (off_t)off);
+        if (r <= 0) die(what, NULL);
+        p += r; n -= (uint64_t)r; off += (uint64_t)r;
+    }
+}
+
+static double parse_bound(const char *s, const char *what)
+{
+    char *e = NULL;
+    errno = 0;
+    const double v = strtod(s, &e);
+    if (e == s || *e || errno || !(v >= 0.0) || isinf(v)) die(what, NULL);
+    return v;
+}
+
+static void print_index(const char *key, uint64_t v)
+{
+    if (v == UINT64_MAX) printf("%s none\n", key);
+    else printf("%s %" PRIu64 "\n", key, v);
+}
+
+static double rmse_of(const mrcz_compare_t *t) { return t->n_finite ? sqrt(t->sum_err2 / (double)t->n_finite) : 0.0; }
+
+int main(int argc, char *argv[])
+{
+    const char *orig = NULL, *zip = NULL, *dtype = "float";
+    double eps_abs = -1.0, eps_rel = -1.0;
+    int opt, device = 0, per_chunk = 0;
+    if (argc < 2) { usage(argv[0]); return 255; }
+    while ((opt = getopt(argc, argv, "ha:z:e:r:s:cg:")) != -1) {
+        switch (opt) {
+        case 'a': orig = optarg; break;
+        case 'z': zip = optarg; break;
+        case 'e': eps_abs = parse_bound(optarg, "-e wants a finite number >= 0"); break;
+        case 'r': eps_rel = parse_bound(optarg, "-r wants a finite number >= 0"); break;
+        case 's': dtype = optarg; break;
+        case 'c': per_chunk = 1; break;
+        case 'g': device = atoi(optarg); break;
+        case 'h': usage(argv[0]); return 0;
+        default: usage(argv[0]); return 255;
+        }
+    }
+    if (!orig || !zip) { usage(argv[0]); die("need -a and -z", NULL); }
+    const int int_mode = strcmp(dtype, "int") == 0;
+    if (!int_mode && strcmp(dtype, "float") != 0) die("-s must be float or int", NULL);
+
+    const int fz = open(zip, O_RDONLY);
+    if (fz < 0) die("cannot open the container", NULL);
+    uint8_t fh[MRCZ_FILE_HEADER_BYTES]; /* write_mrczip_header: u64 fsz, u32 chk, i8 type, i8 ztypes[4] */
+    pread_all(fz, fh, sizeof fh, 0, "container shorter than its 17-byte header");
+    uint64_t fsz = 0;
+    uint32_t chk32 = 0;
+    signed char ztypes[4];
+    memcpy(&fsz, fh, 8);
+    memcpy(&chk32, fh + 8, 4);
+    memcpy(ztypes, fh + 13, 4);
+    if (chk32 == 0 || chk32 > MRCZ_CHUNK_FLOATS) die("chunk size in the file header out of range", NULL);
+    for (int j = 0; j < 4; j++)
+        if (ztypes[j] != 0 && ztypes[j] != 2 && ztypes[j] != 4) die("unknown byte stream compressor type in the file header", NULL);
+    const int fa = open(orig, O_RDONLY);
+    struct stat st;
+    if (fa < 0 || fstat(fa, &st) != 0) die("cannot open the original", NULL);
+    if ((uint64_t)st.st_size != fsz) die("the original's size is not the size the container records", NULL);
+    const uint64_t nfl = fsz / 4, chk = chk32, nch = (nfl + chk - 1) / chk;
+
+    /* record offsets from the 16-byte chunk headers */
+    uint64_t *offs = (uint64_t *)malloc(8u * (size_t)(nch + 1));
+    if (!offs) die("out of memory", NULL);
+    uint64_t off = MRCZ_FILE_HEADER_BYTES, biggest = 0;
+    for (uint64_t k = 0; k < nch; k++) {
+        uint8_t h[16];
+        uint64_t bytes = 0;
+        const uint64_t left = nfl - k * chk;
+        offs[k] = off;
+        pread_all(fz, h, 16, off, "truncated container (chunk header)");
+        if (mrcz_record_size(h, (uint32_t)(left < chk ? left : chk), &bytes) != MRCZ_OK) die("damaged chunk header", NULL);
+        off += bytes;
+    }
+    offs[nch] = off;
+    const uint32_t batch = (uint32_t)(nch < BATCH ? (nch ? nch : 1u) : BATCH);
+    for (uint64_t k = 0; k < nch; k += batch) { /* the largest run sizes the record buffers */
+        const uint64_t e = k + batch < nch ? k + batch : nch;
+        if (offs[e] - offs[k] > biggest) biggest = offs[e] - offs[k];
+    }
+
+    mrcz_ctx_t *c = NULL;
+    if (mrcz_create(&c, device, batch) != MRCZ_OK) die("no usable HIP device (the codec has no CPU path)", NULL);
+    if (mrcz_set_ztypes(c, ztypes) != MRCZ_OK) die("byte stream compressor types", c);
+    mrcz_compare_t total, *chunks = (mrcz_compare_t *)malloc(sizeof(mrcz_compare_t) * (size_t)(nch ? nch : 1));
+    void *h_rec = NULL, *d_rec = NULL, *h_org = NULL, *d_org = NULL, *d_acc = NULL;
+    const uint64_t run_bytes = 4 * chk * batch;
+    if (!chunks || mrcz_dev_malloc(c, &d_acc, sizeof(mrcz_compare_t) * (nch ? nch : 1))) die("out of memory", c);
+    if (nch && (mrcz_host_malloc(c, &h_rec, biggest) || mrcz_dev_malloc(c, &d_rec, biggest) || mrcz_host_malloc(c, &h_org, run_bytes) ||
+                mrcz_dev_malloc(c, &d_org, run_bytes)))
+        die("out of memory", c);
+    for (uint64_t k = 0; k < nch; k += batch) { /* one read of each file and one compare call per run of at most `batch` chunks */
+        const uint64_t e = k + batch < nch ? k + batch : nch, len = offs[e] - offs[k];
+        const uint64_t w0 = k * chk, w1 = e * chk < nfl ? e * chk : nfl;
+        pread_all(fz, h_rec, len, offs[k], "truncated container (payload)");
+        pread_all(fa, h_org, 4 * (w1 - w0), 4 * w0, "read of the original");
+        if (mrcz_copy_h2d(c, d_rec, h_rec, len) != MRCZ_OK || mrcz_copy_h2d(c, d_org, h_org, 4 * (w1 - w0)) != MRCZ_OK) die("copy to the device", c);
+        if (mrcz_uncompress_compare(c, d_rec, len, nfl, chk32, k, e - k, d_org, eps_abs, eps_rel, int_mode, (mrcz_compare_t *)d_acc) != MRCZ_OK)
+            die("compare decode", c);
+    }
+    if (mrcz_compare_finish(c, (const mrcz_compare_t *)d_acc, 0, nch, &total) != MRCZ_OK) die("compare finish", c);
+    if (per_chunk && nch && mrcz_copy_d2h(c, chunks, d_acc, sizeof(mrcz_compare_t) * nch) != MRCZ_OK) die("copy from the device", c);
+
+    const double rmse = rmse_of(&total);
+    printf("n %" PRIu64 "\n", total.n);
+    printf("n_header_diff %" PRIu64 "\n", total.n_header_diff);
+    printf("n_diff %" PRIu64 "\n", total.n_diff);
+    printf("n_finite %" PRIu64 "\n", total.n_finite);
+    printf("n_special_diff %" PRIu64 "\n", total.n_special_diff);
+    printf("n_over_abs %" PRIu64 "\n", total.n_over_abs);
+    printf("n_over_rel %" PRIu64 "\n", total.n_over_rel);
+    print_index("first_over", total.first_over);
+    print_index("max_err_index", total.max_err_index);
+    print_index("max_rel_index", total.max_rel_index);
+    printf("max_err %.17g\nmax_rel %.17g\n", total.max_err, total.max_rel);
+    printf("sum_err %.17g\nsum_abs_err %.17g\nsum_err2 %.17g\n", total.sum_err, total.sum_abs_err, total.sum_err2);
+    printf("orig_min %.17g\norig_max %.17g\norig_sum %.17g\norig_sum2 %.17g\n", total.orig_min, total.orig_max, total.orig_sum, total.orig_sum2);
+    printf("mean_err %.17g\n", total.n_finite ? total.sum_err / (double)total.n_finite : 0.0);
+    printf("rmse %.17g\n", rmse);
+    if (rmse == 0.0) printf("psnr_db inf\n");
+    else printf("psnr_db %.17g\n", 20.0 * log10((total.orig_max - total.orig_min) / rmse));
+    if (per_chunk)
+        for (uint64_t k = 0; k < nch; k++) printf("chunk %" PRIu64 " %.17g %.17g %" PRIu64 "\n", k, chunks[k].max_err, rmse_of(&chunks[k]), chunks[k].n_diff);
+    const int bounded = eps_abs >= 0.0 || eps_rel >= 0.0;
+    const int ok = total.n_header_diff == 0 && (!bounded || (total.n_over_abs == 0 && total.n_over_rel == 0 && total.n_special_diff == 0));
+    if (!ok) {
+        if (total.n_header_diff) printf("FAILED: %" PRIu64 " header words differ\n", total.n_header_diff);
+        if (bounded && total.first_over != UINT64_MAX) printf("FAILED: first word outside the bound: %" PRIu64 "\n", total.first_over);
+    }
+    close(fa);
+    close(fz);
+    fflush(stdout);
+    _exit(ok ? 0 : 1); /* (as mrc_extract: the process's death releases the device memory) */
+}

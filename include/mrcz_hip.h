@@ -261,6 +261,52 @@ int mrcz_uncompress_binned(mrcz_ctx_t *ctx, const void *d_records, uint64_t len,
                            int int_mode, uint64_t *chunks_decoded);
 int mrcz_binned_finish(mrcz_ctx_t *ctx, const mrcz_bin_geom_t *g, const double *d_acc, float *d_out);
 
+/*
+ * Compare decode: how well a container reproduces its original, decoded chunk by chunk without a buffer of the volume's size and
+ * without writing the decoded words anywhere.  Per data word (file word >= 256), with a the original and b the decoded word
+ * read as float32:  d = (double)b - (double)a,  err = |d|,  rel = |(double)a| > 1e-3 ? err / |(double)a| : 0  (the rule of the
+ * reference's QA tool, src/tool/erroranalysis.c, in double).  Each is one correctly rounded IEEE operation.  A point counts in
+ * the error fields when a and b are both finite; words where either is NaN or +-Inf are compared by bit pattern.  err > eps_abs
+ * and rel > eps_rel are strict; a bound that is negative or NaN switches its check off.  The 256 header words are compared by
+ * bit pattern alone.
+ *   mrcz_uncompress_compare  d_records/len = the records of chunks [first_chunk, first_chunk + nchunks) of a file of nfloats_file
+ *                            words; d_orig (16-byte aligned, device) = the original's words of exactly those chunks:
+ *                            min(nchunks * chk, nfloats_file - first_chunk * chk) words.  The chunks are decoded once, in runs
+ *                            of up to max_batch_chunks, and chunk c's summary is assigned to d_acc[c] (absolute chunk number:
+ *                            d_acc is the caller's, ceil(nfloats_file / chk) records, device, needs no zeroing).  int_mode and
+ *                            mrcz_set_ztypes apply as in binned decode.  Synchronous.
+ *   mrcz_compare_finish      folds d_acc[first_chunk .. first_chunk + nchunks) into *h_total (host memory): counts added, maxima
+ *                            with the lowest index on ties, first_over the minimum, the sums added in increasing chunk order
+ *                            in double, starting from the first chunk's value.  nchunks == 0 gives the summary of no words.
+ * Contract: a file is one or more mrcz_uncompress_compare calls that cover its chunks, in any order, each chunk once, each with
+ * its own slice of the original (so a file larger than device memory streams through), then one mrcz_compare_finish.  The bits
+ * of d_acc[c], the sums included, depend on chunk c's words and the bounds only: not on max_batch_chunks, on how the chunks are
+ * split over calls, or on first_chunk (the order in which a chunk's points are added is fixed by their place in the chunk; no
+ * atomics).  MRCZ_EINVAL: a NULL pointer, a misaligned d_orig, first_chunk + nchunks past the file; MRCZ_EFORMAT: chk of 0 or
+ * above MRCZ_CHUNK_FLOATS, malformed streams, records that end before the last chunk's record does (never read past len).
+ * nchunks == 0 is MRCZ_OK and touches nothing.
+ */
+typedef struct mrcz_compare {       /* one chunk's summary, or a whole file's */
+    uint64_t n;               /* data words compared: file words >= 256 of the chunk */
+    uint64_t n_header_diff;   /* file words < 256 whose bit patterns differ */
+    uint64_t n_diff;          /* data words whose bit patterns differ */
+    uint64_t n_finite;        /* data words where original and decoded are both finite: the points of all fields below */
+    uint64_t n_special_diff;  /* data words where either is NaN or +-Inf and the bit patterns differ */
+    uint64_t n_over_abs;      /* finite points with err > eps_abs */
+    uint64_t n_over_rel;      /* finite points with rel > eps_rel */
+    uint64_t first_over;      /* lowest file word index counted in n_over_abs, n_over_rel or n_special_diff; UINT64_MAX: none */
+    uint64_t max_err_index;   /* lowest file word index that attains max_err; UINT64_MAX when n_finite == 0 */
+    uint64_t max_rel_index;   /* likewise for max_rel */
+    double   max_err, max_rel;                    /* 0 when n_finite == 0 */
+    double   sum_err, sum_abs_err, sum_err2;      /* sums of d, |d|, d * d */
+    double   orig_min, orig_max, orig_sum, orig_sum2;  /* of the original at the finite points; +Inf / -Inf / 0 / 0 when none */
+} mrcz_compare_t;
+int mrcz_uncompress_compare(mrcz_ctx_t *ctx, const void *d_records, uint64_t len, uint64_t nfloats_file, uint32_t chk,
+                            uint64_t first_chunk, uint64_t nchunks, const void *d_orig, double eps_abs, double eps_rel,
+                            int int_mode, mrcz_compare_t *d_acc);
+int mrcz_compare_finish(mrcz_ctx_t *ctx, const mrcz_compare_t *d_acc, uint64_t first_chunk, uint64_t nchunks,
+                        mrcz_compare_t *h_total);
+
 /* apply_mask alone on device (the erasebytes restatement used by the GPU-side verification tools,
  * src/tool/erasebytes.c:109-134): words [256, nwords) of a file &= mask(bits).  In place. */
 int mrcz_erase_bits(mrcz_ctx_t *ctx, void *d_words, uint64_t nwords, uint64_t first_word_index, int bits);
