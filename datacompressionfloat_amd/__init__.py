@@ -12,6 +12,9 @@ from .codec import (  # noqa: F401
     MRC_HEADER_BYTES,
     MrcZipCodec,
     MrczError,
+    crc32_combine,
+    format_sidecar,
     pack_file_header,
+    parse_sidecar,
     unpack_file_header,
 )

@@ -31,6 +31,14 @@ class MrczCompare(ctypes.Structure):
                                                "orig_sum", "orig_sum2")]
 
 
+class MrczDigest(ctypes.Structure):
+    """mrcz_digest_t: the CRC-32 of what one chunk, or a whole file, decodes to"""
+    _fields_ = [("crc32", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("nbytes", ctypes.c_uint64)]
+
+
+DIGEST_NONE, DIGEST_MASK, DIGEST_INT8, DIGEST_ABS = 0, 1, 2, 3  # MRCZ_DIGEST_*
+
+
 def load():
     if not os.path.exists(LIB_PATH):
         raise MrczLibraryMissing(
@@ -83,6 +91,15 @@ def load():
     lib.mrcz_uncompress_compare.argtypes = [vp, vp, u64, u64, u32, u64, u64, vp, ctypes.c_double, ctypes.c_double, i32, vp]
     lib.mrcz_compare_finish.restype = i32
     lib.mrcz_compare_finish.argtypes = [vp, vp, u64, u64, ctypes.POINTER(MrczCompare)]
+    lib.mrcz_crc32_combine.restype = u32
+    lib.mrcz_crc32_combine.argtypes = [u32, u32, u64]
+    lib.mrcz_uncompress_digest.restype = i32
+    lib.mrcz_uncompress_digest.argtypes = [vp, vp, u64, u64, u32, u64, u64, i32, vp]
+    for f in (lib.mrcz_digest_words, lib.mrcz_digest_words_async):
+        f.restype = i32
+        f.argtypes = [vp, vp, u64, u64, u32, i32, i32, ctypes.c_float, vp]
+    lib.mrcz_digest_finish.restype = i32
+    lib.mrcz_digest_finish.argtypes = [vp, vp, u64, u64, ctypes.POINTER(MrczDigest)]
     lib.mrcz_generate_kat_words.restype = i32
     lib.mrcz_generate_kat_words.argtypes = [vp, vp, u64, u64]
     lib.mrcz_set_ztypes.restype = i32
@@ -116,4 +133,5 @@ EXPORTS = [
     "mrcz_bin_chunks", "mrcz_uncompress_binned", "mrcz_binned_finish",
     "mrcz_compress_chunks_abs", "mrcz_compress_chunks_abs_async", "mrcz_erase_abs",
     "mrcz_uncompress_compare", "mrcz_compare_finish",
+    "mrcz_crc32_combine", "mrcz_uncompress_digest", "mrcz_digest_words", "mrcz_digest_words_async", "mrcz_digest_finish",
 ]

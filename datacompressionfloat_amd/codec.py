@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MrczBinGeom, MrczBoxGeom, MrczCompare
+from ._lib import DIGEST_ABS, DIGEST_INT8, DIGEST_MASK, DIGEST_NONE, MrczBinGeom, MrczBoxGeom, MrczCompare, MrczDigest
 
 CHUNK_FLOATS = 6 * 1048576  # src/include/constant.h:25
 FILE_HEADER_BYTES = 17      # src/core/common.c:137-148
@@ -55,6 +55,57 @@ def unpack_file_header(buf: bytes):
         raise MrczError("container shorter than the 17-byte header")
     fsz, chk, typ, z0, z1, z2, z3 = struct.unpack("<QIb4b", bytes(buf[:FILE_HEADER_BYTES]))
     return fsz, chk, typ, (z0, z1, z2, z3)
+
+
+def crc32_combine(crc_a: int, crc_b: int, nbytes_b: int) -> int:
+    """zlib.crc32(A + B) from zlib.crc32(A), zlib.crc32(B) and len(B) (mrcz_crc32_combine: host arithmetic, no GPU)"""
+    return int(_LIB.mrcz_crc32_combine(crc_a & 0xFFFFFFFF, crc_b & 0xFFFFFFFF, nbytes_b))
+
+
+SIDECAR_MAGIC = "mrcz-digest crc32 1"
+
+
+def format_sidecar(nfl: int, chk: int, mode: str, file_crc: int, chunk_crcs) -> str:
+    """the digest sidecar of a container: text, one line per chunk"""
+    if mode not in ("float", "int"):
+        raise MrczError("mode must be 'float' or 'int' (mrc_tar -s)")
+    lines = [SIDECAR_MAGIC, f"words {nfl} chunk {chk} chunks {len(chunk_crcs)} mode {mode}", f"file {file_crc & 0xFFFFFFFF:08x}"]
+    lines += [f"{c} {v & 0xFFFFFFFF:08x}" for c, v in enumerate(chunk_crcs)]
+    return "\n".join(lines) + "\n"
+
+
+def parse_sidecar(text) -> dict:
+    """{"words", "chunk", "chunks", "mode", "file", "crcs"} of a sidecar; MrczError for anything that is not one"""
+    if isinstance(text, (bytes, bytearray)):
+        try:
+            text = bytes(text).decode("ascii")
+        except UnicodeDecodeError:
+            raise MrczError("not a digest sidecar: not text")
+    lines = text.split("\n")
+    if lines and lines[-1] == "":
+        lines.pop()
+    hexw = lambda t: len(t) == 8 and all(ch in "0123456789abcdef" for ch in t)
+    num = lambda t: t.isascii() and t.isdigit() and len(t) <= 20
+    if len(lines) < 3 or lines[0] != SIDECAR_MAGIC:
+        raise MrczError("not a digest sidecar: first line is not '" + SIDECAR_MAGIC + "'")
+    t = lines[1].split(" ")
+    if len(t) != 8 or t[0::2] != ["words", "chunk", "chunks", "mode"] or not all(num(v) for v in t[1:7:2]) or t[7] not in ("float", "int"):
+        raise MrczError("damaged digest sidecar: line 2")
+    nfl, chk, nch = int(t[1]), int(t[3]), int(t[5])
+    if chk == 0 or nch != (nfl + chk - 1) // chk:
+        raise MrczError("damaged digest sidecar: words, chunk and chunks disagree")
+    f = lines[2].split(" ")
+    if len(f) != 2 or f[0] != "file" or not hexw(f[1]):
+        raise MrczError("damaged digest sidecar: line 3")
+    if len(lines) != 3 + nch:
+        raise MrczError(f"damaged digest sidecar: {len(lines) - 3} chunk lines for {nch} chunks")
+    crcs = []
+    for c, line in enumerate(lines[3:]):
+        p = line.split(" ")
+        if len(p) != 2 or p[0] != str(c) or not hexw(p[1]):
+            raise MrczError(f"damaged digest sidecar: chunk line {c}")
+        crcs.append(int(p[1], 16))
+    return {"words": nfl, "chunk": chk, "chunks": nch, "mode": t[7], "file": int(f[1], 16), "crcs": crcs}
 
 
 class MrcZipCodec:
@@ -338,6 +389,127 @@ class MrcZipCodec:
             return t
         raw = acc.cpu().numpy().tobytes()
         return t, [self._compare_dict(MrczCompare.from_buffer_copy(raw[c * rsz: (c + 1) * rsz])) for c in range(nch)]
+
+    def uncompress_digest_device(self, records: torch.Tensor, nfloats_file: int, acc: torch.Tensor, first_chunk: int = 0, nchunks: int = None,
+                                 chk: int = CHUNK_FLOATS, int_mode: bool = False):
+        """digest decode, one step (mrcz_uncompress_digest): `records` (cuda uint8) = the chunk records of chunks [first_chunk,
+        first_chunk + nchunks) of a file of nfloats_file floats (default: every chunk from first_chunk on).  Assigns the CRC-32 of
+        what chunk c decodes to to record c of `acc`, a cuda uint8 tensor of ceil(nfloats_file / chk) * sizeof(MrczDigest) bytes
+        (no zeroing needed).  Steps cover the chunks in any order, each once; then digest_finish_device."""
+        assert records.is_cuda and records.dtype == torch.uint8 and records.is_contiguous()
+        if nchunks is None:
+            nchunks = max((nfloats_file + chk - 1) // chk - first_chunk, 0)
+        nch = (nfloats_file + chk - 1) // chk
+        assert acc.is_cuda and acc.dtype == torch.uint8 and acc.is_contiguous() and acc.numel() >= nch * ctypes.sizeof(MrczDigest)
+        torch.cuda.current_stream(records.device).synchronize()
+        rc = _LIB.mrcz_uncompress_digest(self._ctx, records.data_ptr(), records.numel(), nfloats_file, chk, first_chunk, nchunks,
+                                         1 if int_mode else 0, acc.data_ptr())
+        if rc != 0:
+            raise self._err("mrcz_uncompress_digest", rc)
+
+    def digest_words_device(self, words: torch.Tensor, xform=None, bits: int = 0, abs_err=None, first_chunk: int = 0, acc: torch.Tensor = None,
+                            chk: int = CHUNK_FLOATS) -> torch.Tensor:
+        """the chunk digests of words that are on the device (mrcz_digest_words): `words` (cuda, 4-byte elements) holds a file's
+        words from chunk first_chunk on.  xform None: the CRC-32 of the words as they are (a plain file); "mask" (bits), "abs"
+        (abs_err) or "int": of what a container written from them in that mode will decode to.  Returns `acc` (allocated when
+        None): record first_chunk + i is chunk i of `words`; then digest_finish_device."""
+        assert words.is_cuda and words.is_contiguous() and words.element_size() == 4
+        x = {None: DIGEST_NONE, "none": DIGEST_NONE, "mask": DIGEST_MASK, "int": DIGEST_INT8, "abs": DIGEST_ABS}.get(xform, -1)
+        if x < 0:
+            raise MrczError("xform must be None, 'mask', 'abs' or 'int'")
+        eps = abs_bound(abs_err) if x == DIGEST_ABS else 0.0
+        nch = first_chunk + (words.numel() + chk - 1) // chk
+        if acc is None:
+            acc = torch.empty(max(nch, 1) * ctypes.sizeof(MrczDigest), dtype=torch.uint8, device=words.device)
+        assert acc.is_cuda and acc.dtype == torch.uint8 and acc.is_contiguous() and acc.numel() >= nch * ctypes.sizeof(MrczDigest)
+        torch.cuda.current_stream(words.device).synchronize()
+        rc = _LIB.mrcz_digest_words(self._ctx, words.data_ptr(), words.numel(), first_chunk, chk, x, bits, eps, acc.data_ptr())
+        if rc != 0:
+            raise self._err("mrcz_digest_words", rc)
+        return acc
+
+    def digest_finish_device(self, acc: torch.Tensor, first_chunk: int, nchunks: int, per_chunk: bool = False):
+        """(crc32, nbytes) of chunks [first_chunk, first_chunk + nchunks) of `acc` together (mrcz_digest_finish); per_chunk: also
+        the list of the chunks' crc32"""
+        rsz = ctypes.sizeof(MrczDigest)
+        assert acc.is_cuda and acc.dtype == torch.uint8 and acc.numel() >= (first_chunk + nchunks) * rsz
+        total = MrczDigest()
+        rc = _LIB.mrcz_digest_finish(self._ctx, acc.data_ptr(), first_chunk, nchunks, ctypes.byref(total))
+        if rc != 0:
+            raise self._err("mrcz_digest_finish", rc)
+        if not per_chunk:
+            return total.crc32, total.nbytes
+        raw = acc[first_chunk * rsz: (first_chunk + nchunks) * rsz].cpu().numpy().tobytes()
+        return total.crc32, total.nbytes, [MrczDigest.from_buffer_copy(raw[c * rsz: (c + 1) * rsz]).crc32 for c in range(nchunks)]
+
+    def _record_offsets(self, f, nfl: int, chk: int):
+        """byte offset in the container of every chunk record, and of the end of the last, from the 16-byte chunk headers"""
+        offs, off, size_ = [], FILE_HEADER_BYTES, ctypes.c_uint64()
+        for c in range((nfl + chk - 1) // chk):
+            offs.append(off)
+            f.seek(off)
+            h = f.read(16)
+            if len(h) < 16 or _LIB.mrcz_record_size(h, min(chk, nfl - c * chk), ctypes.byref(size_)) != 0:
+                raise MrczError(f"damaged or truncated container: chunk header {c} at byte {off}")
+            off += size_.value
+        offs.append(off)
+        return offs
+
+    def _digest(self, container_or_path, mode: str):
+        """(nfl, chk, file crc32, chunk crc32s) of a container, its records read and decoded in pieces of max_batch_chunks"""
+        if mode not in ("float", "int"):
+            raise MrczError("mode must be 'float' or 'int' (mrc_tar -s)")
+        with self._open(container_or_path) as f:
+            nfl, chk = self._container_header(f)
+            nch = (nfl + chk - 1) // chk
+            offs = self._record_offsets(f, nfl, chk)
+            acc = torch.empty(max(nch, 1) * ctypes.sizeof(MrczDigest), dtype=torch.uint8, device=self.device)
+            step = max(int(self.max_batch_chunks), 1)
+            for k in range(0, nch, step):
+                e = min(k + step, nch)
+                f.seek(offs[k])
+                body = f.read(offs[e] - offs[k])
+                if len(body) != offs[e] - offs[k]:
+                    raise MrczError("truncated container: the records end early")
+                rec = torch.frombuffer(bytearray(body), dtype=torch.uint8).to(self.device)
+                self.uncompress_digest_device(rec, nfl, acc, first_chunk=k, nchunks=e - k, chk=chk, int_mode=(mode == "int"))
+                del rec
+            crc, _, chunks = self.digest_finish_device(acc, 0, nch, per_chunk=True)
+        return nfl, chk, crc, chunks
+
+    def digest(self, container_or_path, mode: str = "float", per_chunk: bool = False):
+        """zlib.crc32 of the file a container (bytes or a path) decodes to, without holding the decoded volume: the records are
+        read and decoded in pieces of at most max_batch_chunks chunks.  per_chunk: (crc32, list of the chunks' crc32)."""
+        _, _, crc, chunks = self._digest(container_or_path, mode)
+        return (crc, chunks) if per_chunk else crc
+
+    def write_sidecar(self, container_or_path, sidecar_path=None, mode: str = "float") -> str:
+        """the digest sidecar of a container as text; written to sidecar_path when given"""
+        nfl, chk, crc, chunks = self._digest(container_or_path, mode)
+        text = format_sidecar(nfl, chk, mode, crc, chunks)
+        if sidecar_path is not None:
+            with open(sidecar_path, "w", newline="\n") as g:
+                g.write(text)
+        return text
+
+    def check_sidecar(self, container_or_path, sidecar, mode: str = None) -> dict:
+        """a container against a sidecar (its text as str with its newlines or as bytes, or a path as os.PathLike or one-line str): {"ok", "file_expected", "file_got", "differing": [(chunk, expected,
+        got)]}.  mode None: the sidecar's.  MrczError when the sidecar is not one or belongs to a file of other words, chunk
+        size or chunks than the container's header names."""
+        if isinstance(sidecar, os.PathLike) or (isinstance(sidecar, str) and "\n" not in sidecar):   # a path; text has lines
+            try:
+                with open(sidecar, "rb") as g:
+                    sidecar = g.read()
+            except OSError as e:
+                raise MrczError(f"cannot read the sidecar: {e}")
+        sc = parse_sidecar(sidecar)
+        with self._open(container_or_path) as f:
+            nfl, chk = self._container_header(f)
+        if (sc["words"], sc["chunk"]) != (nfl, chk):
+            raise MrczError(f"the sidecar is of a file of {sc['words']} words in chunks of {sc['chunk']}, the container holds {nfl} in chunks of {chk}")
+        _, _, crc, chunks = self._digest(container_or_path, mode or sc["mode"])
+        bad = [(c, e, g) for c, (e, g) in enumerate(zip(sc["crcs"], chunks)) if e != g]
+        return {"ok": not bad and crc == sc["file"], "file_expected": sc["file"], "file_got": crc, "differing": bad}
 
     def erase_bits_device(self, words: torch.Tensor, bits: int, first_word_index: int = 0):
         assert words.is_cuda and words.element_size() == 4

@@ -94,6 +94,7 @@ struct mrcz_ctx {
     uint8_t *planes;       /* byte planes of one batch (stream s at s * CHK), both directions; allocated on first use */
     uint32_t *stage;       /* box and binned decode: the words of one batch (max_chunks x CHK); allocated on first use */
     CmpPart *cmp_part;     /* compare decode: CMP_WGS partial summaries per chunk of a batch; allocated on first use */
+    uint32_t *crc_part;    /* digest decode: CRC_ROW words per chunk of a batch (slice remainders, last words); allocated on first use */
     uint32_t *boxbuf;      /* box decode: origins and box lists of a call (boxbuf_words words) */
     uint64_t boxbuf_words;
     /* timing */
@@ -242,6 +243,7 @@ extern "C" void mrcz_destroy(mrcz_ctx_t *ctx)
     (void)hipFree(ctx->planes);
     (void)hipFree(ctx->stage);
     (void)hipFree(ctx->cmp_part);
+    (void)hipFree(ctx->crc_part);
     (void)hipFree(ctx->boxbuf);
     (void)hipFree(ctx->errhist);
     if (ctx->h_result) (void)hipHostFree(ctx->h_result);
@@ -802,6 +804,9 @@ extern "C" int mrcz_uncompress_range_async(mrcz_ctx_t *ctx, const void *d_record
 
 /* ---- compare decode: an error summary per chunk against the original's words, through the same staging buffer ---- */
 #include "mrcz_compare.hip"
+
+/* ---- digest decode: the CRC-32 of what every chunk decodes to, through the same staging buffer ---- */
+#include "mrcz_digest.hip"
 
 /* ---- events and the three streams of a context (pipelines: include/mrcz_hip.h) ---- */
 struct mrcz_event { hipEvent_t ev; };

@@ -10,6 +10,18 @@
  *   -s   decode mode, as mrc_tar -s (the container does not record it)
  *   -c   one line per chunk as well: "chunk c max_err rmse n_diff", the error profile along the file
  *
+ * Digest decode, the fixity check that needs no original (the CRC-32, zlib's, of what the container decodes to):
+ *
+ *   mrc_verify -z vol.mrc.zip -k [-s float|int]           prints the container's digest sidecar (sidecar.h) to stdout
+ *   mrc_verify -a vol.mrc -k                              the same for a plain file: its "file" line is what crc32 vol.mrc prints
+ *                                                         when the size is a multiple of four
+ *   mrc_verify -z vol.mrc.zip -K vol.mrc.zip.crc          checks the container against a sidecar: "chunk <c> expected <hex> got <hex>"
+ *                                                         for every chunk that differs, then "file expected <hex> got <hex>"; exit
+ *                                                         status 0 when all match, 1 when any differs.  The mode is the sidecar's
+ *                                                         unless -s is given.  A sidecar of other words, chunk size or chunks than
+ *                                                         the container's header names is refused (255).
+ *   -k / -K exclude -e and -r; nothing is written.
+ *
  * The container is decoded on the device in runs of the context's batch (16 chunks); the original passes through a pinned buffer
  * in the same runs, one mrcz_uncompress_compare per run, one mrcz_compare_finish.  The decoded words are never written anywhere.
  * Prints one "key value" line per field of mrcz_compare_t (include/mrcz_hip.h) and the derived mean_err = sum_err / n_finite,
@@ -18,6 +30,7 @@
  * that verdict fails; 255 for bad arguments, unreadable files and malformed containers.
  */
 #include "../../include/mrcz_hip.h"
+#include "sidecar.h"
 
 #include <errno.h>
 #include <fcntl.h>
@@ -41,6 +54,8 @@ static void usage(const char *prog)
     printf("\t-s\tdata type the container was written with, [float | int], default float\n\n");
     printf("\t-c\tprint the error of every chunk as well\n\n");
     printf("\t-g\tHIP device, default 0\n\n");
+    printf("\t-k\tprint the digest sidecar (CRC-32 of the decode) of the container -z, or of the plain file -a when no -z is given\n\n");
+    printf("\t-K\tcheck the container -z against this sidecar: exit status 0 all chunks match, 1 some differ\n\n");
 }
 
 /* errors leave with the reference's exit(-1) status (255), never through a signal (as mrc_extract) */
@@ -79,13 +94,123 @@ static void print_index(const char *key, uint64_t v)
 
 static double rmse_of(const mrcz_compare_t *t) { return t->n_finite ? sqrt(t->sum_err2 / (double)t->n_finite) : 0.0; }
 
+/* ---- digest decode: -k / -K ---- */
+
+/* the 17-byte file header of an open container (write_mrczip_header: u64 fsz, u32 chk, i8 type, i8 ztypes[4]) */
+static void container_header(int fz, uint64_t *fsz, uint32_t *chk32, signed char ztypes[4])
+{
+    uint8_t fh[MRCZ_FILE_HEADER_BYTES];
+    pread_all(fz, fh, sizeof fh, 0, "container shorter than its 17-byte header");
+    memcpy(fsz, fh, 8);
+    memcpy(chk32, fh + 8, 4);
+    memcpy(ztypes, fh + 13, 4);
+    if (*chk32 == 0 || *chk32 > MRCZ_CHUNK_FLOATS) die("chunk size in the file header out of range", NULL);
+    for (int j = 0; j < 4; j++)
+        if (ztypes[j] != 0 && ztypes[j] != 2 && ztypes[j] != 4) die("unknown byte stream compressor type in the file header", NULL);
+}
+
+/* record offsets offs[0 .. nch] from the 16-byte chunk headers */
+static uint64_t *record_offsets(int fz, uint64_t nfl, uint64_t chk, uint64_t nch)
+{
+    uint64_t *offs = (uint64_t *)malloc(8u * (size_t)(nch + 1));
+    if (!offs) die("out of memory", NULL);
+    uint64_t off = MRCZ_FILE_HEADER_BYTES;
+    for (uint64_t k = 0; k < nch; k++) {
+        uint8_t h[16];
+        uint64_t bytes = 0;
+        const uint64_t left = nfl - k * chk;
+        offs[k] = off;
+        pread_all(fz, h, 16, off, "truncated container (chunk header)");
+        if (mrcz_record_size(h, (uint32_t)(left < chk ? left : chk), &bytes) != MRCZ_OK) die("damaged chunk header", NULL);
+        off += bytes;
+    }
+    offs[nch] = off;
+    return offs;
+}
+
+/* -k: print the sidecar of the container `zip`, or of the plain file `orig` when zip == NULL; -K: check `zip` against `check` */
+static int digest_main(const char *orig, const char *zip, const char *check, const char *dtype, int device)
+{
+    sidecar_t sc;
+    memset(&sc, 0, sizeof sc);
+    if (check) {
+        const char *why = NULL;
+        if (sidecar_read(check, &sc, &why) != 0) die(why, NULL);
+    }
+    int int_mode = check ? sc.int_mode : 0;
+    if (dtype) {
+        int_mode = strcmp(dtype, "int") == 0;
+        if (!int_mode && strcmp(dtype, "float") != 0) die("-s must be float or int", NULL);
+    }
+    const int fd = open(zip ? zip : orig, O_RDONLY);
+    if (fd < 0) die(zip ? "cannot open the container" : "cannot open the file", NULL);
+    uint64_t fsz = 0, *offs = NULL, biggest = 0;
+    uint32_t chk32 = MRCZ_CHUNK_FLOATS;
+    signed char ztypes[4] = {0, 0, 0, 0};
+    if (zip) container_header(fd, &fsz, &chk32, ztypes);
+    else {
+        struct stat st;
+        if (fstat(fd, &st) != 0) die("cannot stat the file", NULL);
+        fsz = (uint64_t)st.st_size;
+    }
+    const uint64_t nfl = fsz / 4, chk = chk32, nch = (nfl + chk - 1) / chk;
+    if (check && (sc.words != nfl || sc.chunk != chk32 || sc.chunks != nch)) die("the sidecar is of another file: words, chunk or chunks differ from the container's header", NULL);
+    const uint32_t batch = (uint32_t)(nch < BATCH ? (nch ? nch : 1u) : BATCH);
+    if (zip) {
+        offs = record_offsets(fd, nfl, chk, nch);
+        for (uint64_t k = 0; k < nch; k += batch) {
+            const uint64_t e = k + batch < nch ? k + batch : nch;
+            if (offs[e] - offs[k] > biggest) biggest = offs[e] - offs[k];
+        }
+    } else
+        biggest = 4 * chk * batch;
+
+    mrcz_ctx_t *c = NULL;
+    if (mrcz_create(&c, device, batch) != MRCZ_OK) die("no usable HIP device (the codec has no CPU path)", NULL);
+    if (mrcz_set_ztypes(c, ztypes) != MRCZ_OK) die("byte stream compressor types", c);
+    mrcz_digest_t total, *chunks = (mrcz_digest_t *)malloc(sizeof(mrcz_digest_t) * (size_t)(nch ? nch : 1));
+    uint32_t *crcs = (uint32_t *)malloc(4u * (size_t)(nch ? nch : 1));
+    void *h_in = NULL, *d_in = NULL, *d_acc = NULL;
+    if (!chunks || !crcs || mrcz_dev_malloc(c, &d_acc, sizeof(mrcz_digest_t) * (nch ? nch : 1))) die("out of memory", c);
+    if (nch && (mrcz_host_malloc(c, &h_in, biggest) || mrcz_dev_malloc(c, &d_in, biggest))) die("out of memory", c);
+    for (uint64_t k = 0; k < nch; k += batch) { /* one read and one digest call per run of at most `batch` chunks */
+        const uint64_t e = k + batch < nch ? k + batch : nch;
+        if (zip) {
+            const uint64_t len = offs[e] - offs[k];
+            pread_all(fd, h_in, len, offs[k], "truncated container (payload)");
+            if (mrcz_copy_h2d(c, d_in, h_in, len) != MRCZ_OK) die("copy to the device", c);
+            if (mrcz_uncompress_digest(c, d_in, len, nfl, chk32, k, e - k, int_mode, (mrcz_digest_t *)d_acc) != MRCZ_OK) die("digest decode", c);
+        } else {
+            const uint64_t w0 = k * chk, w1 = e * chk < nfl ? e * chk : nfl;
+            pread_all(fd, h_in, 4 * (w1 - w0), 4 * w0, "read of the file");
+            if (mrcz_copy_h2d(c, d_in, h_in, 4 * (w1 - w0)) != MRCZ_OK) die("copy to the device", c);
+            if (mrcz_digest_words(c, d_in, w1 - w0, k, chk32, MRCZ_DIGEST_NONE, 0, 0.0f, (mrcz_digest_t *)d_acc) != MRCZ_OK) die("digest", c);
+        }
+    }
+    if (mrcz_digest_finish(c, (const mrcz_digest_t *)d_acc, 0, nch, &total) != MRCZ_OK) die("digest finish", c);
+    if (nch && mrcz_copy_d2h(c, chunks, d_acc, sizeof(mrcz_digest_t) * nch) != MRCZ_OK) die("copy from the device", c);
+    for (uint64_t k = 0; k < nch; k++) crcs[k] = chunks[k].crc32;
+    int ok = 1;
+    if (!check) {
+        if (sidecar_write(stdout, nfl, chk32, nch, int_mode, total.crc32, crcs) != 0) die("write to stdout", NULL);
+    } else {
+        for (uint64_t k = 0; k < nch; k++)
+            if (crcs[k] != sc.crcs[k]) { ok = 0; printf("chunk %" PRIu64 " expected %08" PRIx32 " got %08" PRIx32 "\n", k, sc.crcs[k], crcs[k]); }
+        if (total.crc32 != sc.file) ok = 0;
+        printf("file expected %08" PRIx32 " got %08" PRIx32 "\n", sc.file, total.crc32);
+    }
+    close(fd);
+    fflush(stdout);
+    _exit(ok ? 0 : 1);
+}
+
 int main(int argc, char *argv[])
 {
-    const char *orig = NULL, *zip = NULL, *dtype = "float";
+    const char *orig = NULL, *zip = NULL, *dtype = NULL, *check = NULL;
     double eps_abs = -1.0, eps_rel = -1.0;
-    int opt, device = 0, per_chunk = 0;
+    int opt, device = 0, per_chunk = 0, print_digest = 0;
     if (argc < 2) { usage(argv[0]); return 255; }
-    while ((opt = getopt(argc, argv, "ha:z:e:r:s:cg:")) != -1) {
+    while ((opt = getopt(argc, argv, "ha:z:e:r:s:cg:kK:")) != -1) {
         switch (opt) {
         case 'a': orig = optarg; break;
         case 'z': zip = optarg; break;
@@ -94,11 +219,21 @@ int main(int argc, char *argv[])
         case 's': dtype = optarg; break;
         case 'c': per_chunk = 1; break;
         case 'g': device = atoi(optarg); break;
+        case 'k': print_digest = 1; break;
+        case 'K': check = optarg; break;
         case 'h': usage(argv[0]); return 0;
         default: usage(argv[0]); return 255;
         }
     }
+    if (print_digest || check) {
+        if (eps_abs >= 0.0 || eps_rel >= 0.0 || per_chunk) die("-k and -K exclude -e, -r and -c", NULL);
+        if (print_digest && check) die("-k prints a sidecar, -K checks one: give one of them", NULL);
+        if (check && (!zip || orig)) die("-K checks a container: give -z and no -a", NULL);
+        if (print_digest && !zip == !orig) die("-k wants a container (-z) or a plain file (-a), not both", NULL);
+        return digest_main(orig, zip, check, dtype, device);
+    }
     if (!orig || !zip) { usage(argv[0]); die("need -a and -z", NULL); }
+    if (!dtype) dtype = "float";
     const int int_mode = strcmp(dtype, "int") == 0;
     if (!int_mode && strcmp(dtype, "float") != 0) die("-s must be float or int", NULL);
 

@@ -73,6 +73,18 @@ int mrcz_workers_set_abs_error(double eps)
     g_abs_eps = f;
     return 0;
 }
+static int g_digest = 0;            /* run_compress / run_uncompress also digest their batches (mrcz_workers_set_digest) */
+static __thread uint32_t *t_crcs;   /* chunk digests of the calling thread's last call, in file order */
+static __thread uint64_t t_ncrc;
+static __thread uint32_t t_file_crc;
+void mrcz_workers_set_digest(int on) { g_digest = on ? 1 : 0; }
+uint64_t mrcz_workers_last_digest(const uint32_t **crcs, uint32_t *file_crc)
+{
+    if (crcs) *crcs = t_crcs;
+    if (file_crc) *file_crc = t_file_crc;
+    return t_ncrc;
+}
+
 static int batch_chunks(void) /* MRCZ_BATCH_CHUNKS overrides the default (tests: several batches from small files) */
 {
     const char *e = getenv("MRCZ_BATCH_CHUNKS");
@@ -301,6 +313,8 @@ typedef struct {
     int decode;           /* 0 = run_compress, 1 = run_uncompress */
     int int_mode;         /* dataConvertedType == "int" (workers.c:782-787, 604-609) */
     float abs_eps;        /* compress: absolute-error bound (mrcz_workers_set_abs_error), 0 = off */
+    int digest;           /* also digest every batch (mrcz_workers_set_digest) into d_dig[device]: one record per chunk of the file */
+    void *d_dig[MAXND];
     signed char ztypes[4];/* decode: compressor types of the four byte streams (file header) */
     int bits;
     uint32_t chk;         /* floats per chunk */
@@ -710,6 +724,9 @@ static void run_pipeline(pipe_t *p)
         pthread_mutex_lock(&D->e->mu);
         CK(mrcz_stream_wait_event(c, MRCZ_STREAM_COMPUTE, D->up_ev[b]), "stream wait", c);
         if (k >= inflight) CK(mrcz_stream_wait_event(c, MRCZ_STREAM_COMPUTE, D->down_ev[b]), "stream wait", c);
+        if (p->digest && !p->decode) /* the expected decode of the batch, while it is resident for the compress */
+            CK(mrcz_digest_words_async(c, D->d_a[b], bt.units, bt.first_chunk, p->chk, p->abs_eps > 0.0f ? MRCZ_DIGEST_ABS : p->int_mode ? MRCZ_DIGEST_INT8 : MRCZ_DIGEST_MASK,
+                                       p->bits, p->abs_eps, (mrcz_digest_t *)p->d_dig[di]), "digest", c);
         if (!p->decode && p->abs_eps > 0.0f)
             CK(mrcz_compress_chunks_abs_async(c, D->d_a[b], bt.units, bt.first_chunk, p->abs_eps, D->d_b[b], rec_cap, D->h_res[b]), "compress", c);
         else if (!p->decode && !p->int_mode)
@@ -721,6 +738,8 @@ static void run_pipeline(pipe_t *p)
             CK(mrcz_uncompress_chunks_async(c, D->d_a[b], bt.in_bytes, bt.units, p->chk, D->d_b[b], D->h_res[b]), "uncompress", c);
         else
             CK(mrcz_uncompress_chunks_int8_async(c, D->d_a[b], bt.in_bytes, bt.units, p->chk, bt.first_chunk, D->d_b[b], D->h_res[b]), "uncompress", c);
+        if (p->digest && p->decode) /* the decoded batch, before it is downloaded */
+            CK(mrcz_digest_words_async(c, D->d_b[b], bt.units, bt.first_chunk, p->chk, MRCZ_DIGEST_NONE, 0, 0.0f, (mrcz_digest_t *)p->d_dig[di]), "digest", c);
         CK(mrcz_event_record(c, MRCZ_STREAM_COMPUTE, D->comp_ev[b]), "event record", c);
         pthread_mutex_unlock(&D->e->mu);
         pthread_mutex_lock(&p->mu);
@@ -736,6 +755,38 @@ static void run_pipeline(pipe_t *p)
     __sync_sub_and_fetch(&g_pipes_active, 1);
     pthread_mutex_destroy(&p->mu);
     pthread_cond_destroy(&p->cv);
+}
+
+/* The chunk digests of a finished pipeline in file order: batch k (chunks k * batch_chunks ...) left its records on device
+ * k % nd.  One small copy per device after the last batch; then the file's digest by mrcz_crc32_combine. */
+static void digest_collect(pipe_t *p, uint64_t file_chunks)
+{
+    mrcz_digest_t *h = (mrcz_digest_t *)malloc(sizeof(mrcz_digest_t) * (size_t)file_chunks);
+    uint32_t *crcs = (uint32_t *)realloc(t_crcs, 4u * (size_t)file_chunks);
+    if (!h || !crcs) die("fail to alloc mem", NULL);
+    t_crcs = crcs;
+    const uint64_t bc = (uint64_t)p->batch_chunks;
+    for (int di = 0; di < p->nd; di++) {
+        engine_t *e = p->s->d[di].e;
+        pthread_mutex_lock(&e->mu);
+        CK(mrcz_copy_d2h(e->c, h, p->d_dig[di], sizeof(mrcz_digest_t) * file_chunks), "D2H copy", e->c);
+        CK(mrcz_dev_free(e->c, p->d_dig[di]), "free", e->c);
+        pthread_mutex_unlock(&e->mu);
+        for (uint64_t k = (uint64_t)di; k * bc < file_chunks; k += (uint64_t)p->nd)
+            for (uint64_t ch = k * bc; ch < (k + 1) * bc && ch < file_chunks; ch++) {
+                const uint64_t left = p->total_floats - ch * p->chk, n = left < p->chk ? left : p->chk;
+                if (h[ch].nbytes != 4u * n) die("digest: a chunk's record was not written", NULL);
+                crcs[ch] = h[ch].crc32;
+            }
+    }
+    uint32_t file = 0;
+    for (uint64_t ch = 0; ch < file_chunks; ch++) {
+        const uint64_t left = p->total_floats - ch * p->chk;
+        file = mrcz_crc32_combine(file, crcs[ch], 4u * (left < p->chk ? left : p->chk));
+    }
+    t_file_crc = file;
+    t_ncrc = file_chunks;
+    free(h);
 }
 
 /* What run_compress and run_uncompress share: size the batches and the devices for the file, take a session, run the pipeline
@@ -755,8 +806,15 @@ static double run_file(pipe_t *p, double begin, const char *what)
     p->nd = nd;
     p->batch_chunks = batch;
     p->fd_out = output_fd(p->fout, &p->out_off);
+    t_ncrc = 0;
+    if (p->digest)
+        for (int di = 0; di < nd; di++) {
+            mrcz_ctx_t *c = p->s->d[di].e->c;
+            CK(mrcz_dev_malloc(c, &p->d_dig[di], file_chunks * sizeof(mrcz_digest_t)), "fail to alloc mem", c);
+        }
     p->t_setup = now_sec() - begin;
     run_pipeline(p);
+    if (p->digest) digest_collect(p, file_chunks);
     session_put(p->s);
     if (p->fd_out >= 0) fseeko(p->fout, (off_t)p->out_off, SEEK_SET); /* the stream continues after what pwrite() wrote */
     const double elapsed = now_sec() - begin;
@@ -768,6 +826,7 @@ int run_compress(FILE *fin, ctx_t *ctx, FILE *fout, const int bitsToMask, const 
 {
     /* workers.c:782: strcmp(dataConvertedType, "int") == 0 selects the int mode, anything else is treated as float */
     const int int_mode = dataConvertedType && strcmp(dataConvertedType, "int") == 0;
+    t_ncrc = 0;
     if (bitsToMask < 0 || bitsToMask > 32) {
         fprintf(stderr, "[%s:%d] ERROR: bits to erase must be in 0..32 (table of 33 masks, workers.c:29-37)\n", __FILE__, __LINE__);
         mrcz_workers_fatal_exit();
@@ -791,6 +850,7 @@ int run_compress(FILE *fin, ctx_t *ctx, FILE *fout, const int bitsToMask, const 
     pipe_t p;
     memset(&p, 0, sizeof(p));
     p.fin = fin; p.fout = fout; p.decode = 0; p.int_mode = int_mode; p.abs_eps = abs_eps; p.bits = bitsToMask; p.chk = CHUNK_SIZE;
+    p.digest = g_digest;
     p.total_floats = file_floats;
     const double elapsed = run_file(&p, begin, "run_compress");
     ctx->zipTime += elapsed;
@@ -804,6 +864,7 @@ int run_compress(FILE *fin, ctx_t *ctx, FILE *fout, const int bitsToMask, const 
 int run_uncompress(FILE *fin, ctx_t *ctx, mrczip_header_t *hd, FILE *fout, const char *dataConvertedType)
 {
     const int int_mode = dataConvertedType && strcmp(dataConvertedType, "int") == 0; /* workers.c:604, 646 */
+    t_ncrc = 0;
     for (int j = 0; j < COMPRESSION_PATH_NUM; j++)
         if (hd->ztypes[j] != 0 && hd->ztypes[j] != 2 && hd->ztypes[j] != 4) { /* ZLIB_DEF, LZ4_DEF, LZ4HC_DEF (mrczip.h:37-40); init_mrc_zip_stream rejects the rest (zip.c:319-321) */
             fprintf(stderr, "[%s:%d] ERROR: byte stream %d uses unknown compressor type %d\n", __FILE__, __LINE__, j, hd->ztypes[j]);
@@ -820,6 +881,7 @@ int run_uncompress(FILE *fin, ctx_t *ctx, mrczip_header_t *hd, FILE *fout, const
     pipe_t p;
     memset(&p, 0, sizeof(p));
     p.fin = fin; p.fout = fout; p.decode = 1; p.int_mode = int_mode; p.chk = hd->chk; p.total_floats = nfloats;
+    p.digest = g_digest;
     memcpy(p.ztypes, hd->ztypes, 4);
     const double elapsed = run_file(&p, begin, "run_uncompress");
     ctx->unzipTime += elapsed;

@@ -307,6 +307,55 @@ int mrcz_uncompress_compare(mrcz_ctx_t *ctx, const void *d_records, uint64_t len
 int mrcz_compare_finish(mrcz_ctx_t *ctx, const mrcz_compare_t *d_acc, uint64_t first_chunk, uint64_t nchunks,
                         mrcz_compare_t *h_total);
 
+/*
+ * Digest decode: the standard CRC-32 (zlib, gzip, PNG, crc32(1): reflected polynomial 0xEDB88320, initial value and final xor
+ * 0xFFFFFFFF) of the bytes a container decodes to, per chunk and for the file, decoded chunk by chunk without a buffer of the
+ * volume's size and without writing the decoded words anywhere.  The container holds no checksum; this is the fixity check of an
+ * archive whose original is gone.  Chunk c's digest is zlib.crc32 of its decoded words as the file holds them (little-endian,
+ * 4 n_c bytes); the file's digest is zlib.crc32 of all floor(fsz / 4) words, i.e. of the restored file.
+ *   mrcz_crc32_combine      crc32(A || B) from crc32(A), crc32(B) and |B| in bytes (any 64-bit count).  Pure host arithmetic:
+ *                           no context, no GPU.
+ *   mrcz_uncompress_digest  d_records/len = the records of chunks [first_chunk, first_chunk + nchunks) of a file of nfloats_file
+ *                           words.  The chunks are decoded once, in runs of up to max_batch_chunks, and chunk c's digest is
+ *                           assigned to d_acc[c] (absolute chunk number: d_acc is the caller's, ceil(nfloats_file / chk)
+ *                           records, device, needs no zeroing).  int_mode and mrcz_set_ztypes apply as in compare decode.
+ *                           Synchronous.
+ *   mrcz_digest_words       the same records for words that are already on the device: d_words (16-byte aligned) holds the
+ *                           file's words from chunk first_chunk on, nwords of them, in chunks of chk.  xform = MRCZ_DIGEST_NONE:
+ *                           the CRC-32 of the words as they are (a plain file).  MRCZ_DIGEST_MASK (bits, 0..32), MRCZ_DIGEST_ABS
+ *                           (eps, as mrcz_compress_chunks_abs) and MRCZ_DIGEST_INT8: the digest of what a container written
+ *                           from these words by mrcz_compress_chunks / _abs / _int8 WILL decode to (file words < 256 keep their
+ *                           bits, as there), without compressing or decoding anything: the value to record when the archive is
+ *                           made.  Synchronous; mrcz_digest_words_async enqueues on the compute stream and returns.
+ *   mrcz_digest_finish      copies d_acc[first_chunk .. first_chunk + nchunks) once and combines the records on the host in chunk
+ *                           order into *h_total (host memory); h_total->nbytes is the sum.  nchunks == 0 gives { 0, 0, 0 }, the
+ *                           CRC-32 of no bytes.
+ * Contract: as compare decode.  A file is one or more mrcz_uncompress_digest calls that cover its chunks, in any order, each
+ * chunk once, then one mrcz_digest_finish.  CRC is exact arithmetic: the bits of d_acc[c] depend on chunk c's decoded words only.
+ * MRCZ_EINVAL: a NULL pointer, a misaligned pointer, first_chunk + nchunks past the file, an unknown xform, bits outside 0..32, an
+ * eps that is not finite and > 0, (digest_words) chk of 0 or above MRCZ_CHUNK_FLOATS; MRCZ_EFORMAT: (uncompress_digest) chk of 0
+ * or above MRCZ_CHUNK_FLOATS, malformed streams, records that end before the last chunk's record does (never read past len).
+ * nchunks == 0 / nwords == 0 is MRCZ_OK and touches nothing.
+ */
+#define MRCZ_DIGEST_NONE 0
+#define MRCZ_DIGEST_MASK 1
+#define MRCZ_DIGEST_INT8 2
+#define MRCZ_DIGEST_ABS 3
+typedef struct mrcz_digest {  /* one chunk's digest, or a whole file's */
+    uint32_t crc32;
+    uint32_t reserved;        /* 0 */
+    uint64_t nbytes;          /* bytes digested */
+} mrcz_digest_t;
+uint32_t mrcz_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t nbytes_b);
+int mrcz_uncompress_digest(mrcz_ctx_t *ctx, const void *d_records, uint64_t len, uint64_t nfloats_file, uint32_t chk,
+                           uint64_t first_chunk, uint64_t nchunks, int int_mode, mrcz_digest_t *d_acc);
+int mrcz_digest_words(mrcz_ctx_t *ctx, const void *d_words, uint64_t nwords, uint64_t first_chunk, uint32_t chk, int xform,
+                      int bits, float eps, mrcz_digest_t *d_acc);
+int mrcz_digest_words_async(mrcz_ctx_t *ctx, const void *d_words, uint64_t nwords, uint64_t first_chunk, uint32_t chk, int xform,
+                            int bits, float eps, mrcz_digest_t *d_acc);
+int mrcz_digest_finish(mrcz_ctx_t *ctx, const mrcz_digest_t *d_acc, uint64_t first_chunk, uint64_t nchunks,
+                       mrcz_digest_t *h_total);
+
 /* apply_mask alone on device (the erasebytes restatement used by the GPU-side verification tools,
  * src/tool/erasebytes.c:109-134): words [256, nwords) of a file &= mask(bits).  In place. */
 int mrcz_erase_bits(mrcz_ctx_t *ctx, void *d_words, uint64_t nwords, uint64_t first_word_index, int bits);

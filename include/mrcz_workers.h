@@ -74,6 +74,15 @@ void mrcz_workers_set_batch_chunks(int chunks);
  * or -1 (setting unchanged) for eps < 0, NaN, Inf or a bound below the smallest float32.  run_compress reads it when it starts and
  * fails, as for a bad bitsToMask, when it is on together with bitsToMask != 0 or the int mode.  Decoding needs nothing. */
 int mrcz_workers_set_abs_error(double eps);
+/* Digest of the pipeline (opt-in; off by default, and then run_compress / run_uncompress enqueue exactly what they enqueue
+ * without it).  When on, run_compress also digests every batch while it is resident for the compress -- the CRC-32 (zlib's) of
+ * what the container being written WILL decode to under the mode in force (bits, absolute error, int) -- and run_uncompress
+ * digests every decoded batch on the device before it is downloaded (mrcz_digest_words_async, include/mrcz_hip.h), on whichever
+ * device the batch was dealt to.  mrcz_workers_last_digest gives the chunk digests of the calling thread's last run_compress /
+ * run_uncompress in file order (crcs: the library's, valid until the thread's next call) and the file's; it returns the number of
+ * chunks, 0 when the digest was off. */
+void mrcz_workers_set_digest(int on);
+uint64_t mrcz_workers_last_digest(const uint32_t **crcs, uint32_t *file_crc);
 /* What the library's own fatal errors leave through (the reference's exit(-1), src/core/workers.c:708-712, adapt.c:34-44): stdio
  * flushed, then _exit(255) -- the errors are raised by pipeline or worker threads while others still use the GPU, and exit
  * handlers run under them crash instead of exiting. */
