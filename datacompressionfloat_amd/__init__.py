@@ -16,5 +16,6 @@ from .codec import (  # noqa: F401
     format_sidecar,
     pack_file_header,
     parse_sidecar,
+    read_thinned_records,
     unpack_file_header,
 )

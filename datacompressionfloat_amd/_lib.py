@@ -37,6 +37,7 @@ class MrczDigest(ctypes.Structure):
 
 
 DIGEST_NONE, DIGEST_MASK, DIGEST_INT8, DIGEST_ABS = 0, 1, 2, 3  # MRCZ_DIGEST_*
+TOP_F32, TOP_U16, TOP_THINNED = 0, 1, 4                         # MRCZ_TOP_*
 
 
 def load():
@@ -100,6 +101,10 @@ def load():
         f.argtypes = [vp, vp, u64, u64, u32, i32, i32, ctypes.c_float, vp]
     lib.mrcz_digest_finish.restype = i32
     lib.mrcz_digest_finish.argtypes = [vp, vp, u64, u64, ctypes.POINTER(MrczDigest)]
+    lib.mrcz_record_top_span.restype = i32
+    lib.mrcz_record_top_span.argtypes = [vp, u32, i32, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.mrcz_uncompress_top.restype = i32
+    lib.mrcz_uncompress_top.argtypes = [vp, vp, u64, u64, u32, u64, u64, i32, i32, vp, ctypes.POINTER(u64)]
     lib.mrcz_generate_kat_words.restype = i32
     lib.mrcz_generate_kat_words.argtypes = [vp, vp, u64, u64]
     lib.mrcz_set_ztypes.restype = i32
@@ -134,4 +139,5 @@ EXPORTS = [
     "mrcz_compress_chunks_abs", "mrcz_compress_chunks_abs_async", "mrcz_erase_abs",
     "mrcz_uncompress_compare", "mrcz_compare_finish",
     "mrcz_crc32_combine", "mrcz_uncompress_digest", "mrcz_digest_words", "mrcz_digest_words_async", "mrcz_digest_finish",
+    "mrcz_record_top_span", "mrcz_uncompress_top", "mrcz_uncompress_top_async",
 ]

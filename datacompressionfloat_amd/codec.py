@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import DIGEST_ABS, DIGEST_INT8, DIGEST_MASK, DIGEST_NONE, MrczBinGeom, MrczBoxGeom, MrczCompare, MrczDigest
+from ._lib import (DIGEST_ABS, DIGEST_INT8, DIGEST_MASK, DIGEST_NONE, TOP_F32, TOP_THINNED, TOP_U16, MrczBinGeom, MrczBoxGeom, MrczCompare,
+                   MrczDigest)
 
 CHUNK_FLOATS = 6 * 1048576  # src/include/constant.h:25
 FILE_HEADER_BYTES = 17      # src/core/common.c:137-148
@@ -106,6 +107,43 @@ def parse_sidecar(text) -> dict:
             raise MrczError(f"damaged digest sidecar: chunk line {c}")
         crcs.append(int(p[1], 16))
     return {"words": nfl, "chunk": chk, "chunks": nch, "mode": t[7], "file": int(f[1], 16), "crcs": crcs}
+
+
+def read_thinned_records(f, nfl: int, chk: int, keep: int, first_chunk: int = 0, nchunks: int = None, start: int = None):
+    """the thinned records of chunks [first_chunk, first_chunk + nchunks) of the container open as binary file `f`:
+    per chunk its 16-byte header and, behind it, the payloads of its `keep` top byte planes, which are the tail of the record
+    (mrcz_record_top_span).  Host arithmetic and reads only, no GPU: the headers are read 16 bytes at a time, the kept payloads
+    with one read per chunk, and no byte of a dropped payload is read.  `start` = the byte offset in `f` of chunk first_chunk's
+    record when the caller knows it (else the headers of the chunks before are walked).  Returns (bytes, offset of the record of
+    chunk first_chunk + nchunks)."""
+    nch = (nfl + chk - 1) // chk
+    if nchunks is None:
+        nchunks = nch - first_chunk
+    if keep not in (2, 3) or first_chunk < 0 or nchunks < 0 or first_chunk + nchunks > nch:
+        raise MrczError("keep must be 2 or 3 and the chunks inside the file")
+    size, skip, kept = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+
+    def header(c, off):
+        f.seek(off)
+        h = f.read(16)
+        if len(h) < 16 or _LIB.mrcz_record_top_span(h, min(chk, nfl - c * chk), keep, ctypes.byref(skip), ctypes.byref(kept)) != 0:
+            raise MrczError(f"damaged or truncated container: chunk header {c} at byte {off}")
+        return h
+
+    off = FILE_HEADER_BYTES if start is None else start
+    for c in range(first_chunk if start is None else 0):
+        header(c, off)
+        off += skip.value + kept.value
+    out = bytearray()
+    for c in range(first_chunk, first_chunk + nchunks):
+        out += header(c, off)
+        f.seek(off + skip.value)
+        body = f.read(kept.value)
+        if len(body) != kept.value:
+            raise MrczError("truncated container: the records end early")
+        out += body
+        off += skip.value + kept.value
+    return bytes(out), off
 
 
 class MrcZipCodec:
@@ -228,6 +266,36 @@ class MrcZipCodec:
         if rc != 0:
             raise self._err("mrcz_uncompress_range", rc)
         return out[:n], int(consumed.value)
+
+    def uncompress_top_device(self, records: torch.Tensor, nfloats_file: int, keep: int = 2, dtype=torch.bfloat16, first_chunk: int = 0,
+                              nchunks: int = None, thinned: bool = False, out: torch.Tensor = None, chk: int = CHUNK_FLOATS):
+        """top-planes decode (mrcz_uncompress_top): the words of chunks [first_chunk, first_chunk + nchunks) of a file of
+        nfloats_file floats (default: every chunk from first_chunk on) with only their `keep` (2 or 3) most significant byte
+        planes; the low planes are neither read nor decoded.  `records` (cuda uint8) = the ordinary records of those chunks, or
+        with thinned=True their thinned records (read_thinned_records).  dtype torch.float32: every word & (0xFFFFFFFF <<
+        8 (4 - keep)); torch.bfloat16 (keep 2 only): the same value in two bytes.  This is TRUNCATION toward zero, not the
+        round-to-nearest of Tensor.to(torch.bfloat16); NaN payload bits in the dropped planes are lost (a NaN whose only set
+        mantissa bits were there becomes +-Inf); file words 0..255 (the MRC header) are truncated like the rest.  Returns a
+        1-D cuda tensor of that dtype (`out`, 16-byte aligned, or allocated)."""
+        assert records.is_cuda and records.dtype == torch.uint8 and records.is_contiguous()
+        if dtype not in (torch.bfloat16, torch.float32):
+            raise MrczError("dtype must be torch.bfloat16 or torch.float32")
+        if keep not in (2, 3) or (dtype == torch.bfloat16 and keep != 2):
+            raise MrczError("keep must be 2 or 3, and torch.bfloat16 holds two planes: keep == 2")
+        if nchunks is None:
+            nchunks = max((nfloats_file + chk - 1) // chk - first_chunk, 0)
+        n = max(min(nchunks * chk, nfloats_file - first_chunk * chk), 0)
+        if out is None:
+            out = torch.empty(max(n, 1), dtype=dtype, device=records.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == dtype and out.numel() >= n
+        torch.cuda.current_stream(records.device).synchronize()
+        flags = (TOP_U16 if dtype == torch.bfloat16 else TOP_F32) | (TOP_THINNED if thinned else 0)
+        consumed = ctypes.c_uint64()
+        rc = _LIB.mrcz_uncompress_top(self._ctx, records.data_ptr(), records.numel(), nfloats_file, chk, first_chunk, nchunks, keep, flags,
+                                      out.data_ptr(), ctypes.byref(consumed))
+        if rc != 0:
+            raise self._err("mrcz_uncompress_top", rc)
+        return out.reshape(-1)[:n]
 
     def uncompress_boxes_device(self, records: torch.Tensor, nfloats_file: int, geom: MrczBoxGeom, origins, first_chunk: int = 0,
                                 nchunks: int = None, out: torch.Tensor = None, int_mode: bool = False, chk: int = CHUNK_FLOATS):
@@ -775,3 +843,43 @@ class MrcZipCodec:
                 self.uncompress_binned_device(rec, nfl, geom, acc, first_chunk=k, nchunks=e - k, int_mode=(mode == "int"), chk=chk)
                 del rec
         return self.binned_finish_device(geom, acc)
+
+    # ---- top-planes decode: bfloat16-precision reads that leave the low byte planes on the disk ----
+    def _top_words(self, f, keep: int, dtype) -> torch.Tensor:
+        """every word of the container open as `f` under the mask of `keep` planes, as a 1-D cuda tensor of `dtype`: thinned
+        records read and decoded in pieces of at most max_batch_chunks chunks"""
+        nfl, chk = self._container_header(f)
+        nch = (nfl + chk - 1) // chk
+        out = torch.empty(max(nfl, 1), dtype=dtype, device=self.device)
+        step, off = max(int(self.max_batch_chunks), 1), FILE_HEADER_BYTES
+        for k in range(0, nch, step):
+            e = min(k + step, nch)
+            body, off = read_thinned_records(f, nfl, chk, keep, k, e - k, start=off)
+            rec = torch.frombuffer(bytearray(body), dtype=torch.uint8).to(self.device)
+            dst = out[k * chk:]
+            if dst.data_ptr() % 16 == 0:
+                self.uncompress_top_device(rec, nfl, keep, dtype, first_chunk=k, nchunks=e - k, thinned=True, out=dst, chk=chk)
+            else:  # a chunk size whose pieces do not start on 16 bytes: through a buffer of the piece's own
+                piece = self.uncompress_top_device(rec, nfl, keep, dtype, first_chunk=k, nchunks=e - k, thinned=True, chk=chk)
+                dst[: piece.numel()] = piece
+            del rec
+        return out[:nfl]
+
+    def unzip_top(self, container_or_path, keep: int = 2, dtype=torch.bfloat16) -> torch.Tensor:
+        """all floor(fsz / 4) words of a container (bytes or a path) with only their `keep` top byte planes, as a 1-D cuda tensor
+        of `dtype` (uncompress_top_device: truncation, the header words included).  Of a path only the file header, the 16-byte
+        chunk headers and the kept payloads are read."""
+        with self._open(container_or_path) as f:
+            return self._top_words(f, keep, dtype)
+
+    def read_mrc_top(self, path, keep: int = 2, dtype=torch.bfloat16) -> torch.Tensor:
+        """a compressed float32 (mode 2) MRC volume at reduced precision, as an (nz, ny, nx) cuda tensor of `dtype`
+        (uncompress_top_device: bfloat16 by truncation for keep 2).  The MRC header comes from a range decode of the first 256
+        words, as in read_mrc_slab; the voxels from thinned records, so the low byte planes of the file are never read."""
+        with self._open(path) as f:
+            nfl, _ = self._container_header(f)
+            d0, nx, ny, nz = self._mrc_volume(f)
+            if d0 + nx * ny * nz > nfl:
+                raise MrczError("the MRC header describes more data than the file holds")
+            words = self._top_words(f, keep, dtype)
+        return words[d0: d0 + nx * ny * nz].reshape(nz, ny, nx)

@@ -600,11 +600,19 @@ static int uncompress_prepare(mrcz_ctx_t *ctx, const void *d_records, uint32_t c
 
 /* parse the records of one batch of nb chunks (bfl floats) where the previous batch stopped (ctx->result[0]) and decode their
  * planes into the workspace; the merge is left to the caller */
+static int decode_streams(mrcz_ctx_t *ctx, const uint8_t *rec, uint64_t len, uint32_t ns);
 static int decode_batch(mrcz_ctx_t *ctx, const uint8_t *rec, uint64_t len, uint64_t bfl, uint32_t nb, uint32_t chk)
 {
     hipStream_t lstream = ctx->stream;
     LAUNCH("k_parse_records", k_parse_records, dim3(1), dim3(64), rec, len, bfl, chk, ctx->dstreams, ctx->result, ctx->lz4_planes);
-    const uint32_t ns = 4 * nb;
+    return decode_streams(ctx, rec, len, 4 * nb);
+}
+
+/* decode the ns streams of the table a record walk left in ctx->dstreams (four per chunk after k_parse_records, the kept planes
+ * alone after k_parse_top: nothing below knows which plane a stream is) */
+static int decode_streams(mrcz_ctx_t *ctx, const uint8_t *rec, uint64_t len, uint32_t ns)
+{
+    hipStream_t lstream = ctx->stream;
     HIPCHK(hipMemsetAsync(ctx->ncand, 0, ns * sizeof(uint32_t), ctx->stream), "memset ncand");
     HIPCHK(hipMemsetAsync(ctx->njobs, 0, (4 + RAW_SEGS) * sizeof(uint32_t), ctx->stream), "memset njobs");
     if (ctx->phase_profile == 2 || ctx->phase_profile == 4) HIPCHK(hipMemsetAsync(ctx->dbgphase, 0, (size_t)ns * 40 * sizeof(unsigned long long), ctx->stream), "memset dbg");
@@ -807,6 +815,9 @@ extern "C" int mrcz_uncompress_range_async(mrcz_ctx_t *ctx, const void *d_record
 
 /* ---- digest decode: the CRC-32 of what every chunk decodes to, through the same staging buffer ---- */
 #include "mrcz_digest.hip"
+
+/* ---- top-planes decode: the two or three most significant byte planes of every word, the others neither read nor decoded ---- */
+#include "mrcz_top.hip"
 
 /* ---- events and the three streams of a context (pipelines: include/mrcz_hip.h) ---- */
 struct mrcz_event { hipEvent_t ev; };

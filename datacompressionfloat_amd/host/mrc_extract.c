@@ -2,8 +2,8 @@
  * mrc_extract.c -- range, box and binned decode from the command line: part of a container without reading or decoding the rest,
  * or a binned overview of it without a buffer of the volume's size.
  *
- *   mrc_extract -i vol.mrc.zip -o out.raw (-w first:count | -z z0:z1 | -B centers.txt -S bx[,by,bz] [-F fill] | -N f[,fy,fz])
- *               [-s float|int] [-g device]
+ *   mrc_extract -i vol.mrc.zip -o out.raw (-w first:count | -z z0:z1 | -B centers.txt -S bx[,by,bz] [-F fill] | -N f[,fy,fz]
+ *               | -P keep [-H]) [-s float|int] [-g device]
  *
  *   -w first:count   words [first, first + count) of the decoded file (4 bytes each)
  *   -z z0:z1         sections [z0, z1) of a float32 (mode 2) MRC volume: nx, ny, nz, mode (bytes 0-15) and nsymbt (bytes 92-95)
@@ -16,6 +16,10 @@
  *   -N f | fx,fy,fz  a float32 MRC volume average-pooled by the bin factors (1 <= f <= the dimension; voxels of a trailing
  *                    remainder of an axis are ignored).  The output is raw float32 in [mz][my][mx] order, (mx, my, mz) =
  *                    (nx / fx, ny / fy, nz / fz): each voxel is the mean of its bin, summed in double in file order
+ *   -P keep          the whole file at reduced precision: every word & (0xFFFFFFFF << 8 (4 - keep)), keep = 2 or 3 top byte planes
+ *                    (2: the bfloat16 truncation of every float32).  The output is raw float32, all floor(fsz / 4) words of the
+ *                    file, the 256 header words truncated like the rest.  Not with -s int (that data lives in plane 0)
+ *   -H               with -P 2: raw 16-bit words instead, word >> 16 (bfloat16 bit patterns), 2 bytes each
  *   -s               decode mode, as mrc_tar -s (the container does not record it)
  *
  * The 17-byte file header and the 16-byte header of every chunk before the window are read with pread; then only the records of
@@ -23,7 +27,9 @@
  * fit in device memory; the workspace is batched as in every decode).  -B reads the chunk headers up to the last chunk a box
  * touches (mrcz_boxes_chunks), then the records of every run of touched chunks, one mrcz_uncompress_boxes call per run.  -N reads
  * the chunk headers up to the last chunk the bins use (mrcz_bin_chunks), then the records of the used chunks in pieces of at
- * most the context's batch (16 chunks), one mrcz_uncompress_binned call per piece, and one mrcz_binned_finish.  Not one of the
+ * most the context's batch (16 chunks), one mrcz_uncompress_binned call per piece, and one mrcz_binned_finish.  -P reads every
+ * chunk header, then per chunk the kept payloads alone (one pread of the record's tail, mrcz_record_top_span) into thinned
+ * records, in pieces of the context's batch: not one byte of a dropped payload is read.  Not one of the
  * reference's front ends: mrc_tar and mrc_tarx keep the reference's command lines.
  */
 #include "../../include/mrcz_hip.h"
@@ -42,7 +48,7 @@
 static void usage(const char *prog)
 {
     printf("\nUsage:\n\n\t%s -i <container> -o <output file> (-w <first>:<count> | -z <z0>:<z1> | -B <centres> -S <bx>[,<by>,<bz>] [-F <fill>]\n"
-           "\t\t| -N <f>[,<fy>,<fz>]) [-s float|int] [-g device]\nwhere:\n", prog);
+           "\t\t| -N <f>[,<fy>,<fz>] | -P <keep> [-H]) [-s float|int] [-g device]\nwhere:\n", prog);
     printf("\t-i\tcontainer written by mrc_tar -t zip\n\n");
     printf("\t-o\traw output: the decoded words of the window, 4 bytes each\n\n");
     printf("\t-w\twords [first, first + count) of the decoded file\n\n");
@@ -53,6 +59,9 @@ static void usage(const char *prog)
     printf("\t-F\tvalue of box voxels outside the volume, default 0\n\n");
     printf("\t-N\ta float32 (mode 2) MRC volume binned (average-pooled) by f, or by fx,fy,fz; remainders are ignored;\n"
            "\t\toutput: raw float32, [nz / fz][ny / fy][nx / fx]\n\n");
+    printf("\t-P\tthe whole file with only its <keep> = 2 or 3 top byte planes (2: bfloat16 precision, truncated); the low planes\n"
+           "\t\tare not read; output: raw float32 with the dropped bytes zero\n\n");
+    printf("\t-H\twith -P 2: raw 16-bit words (bfloat16 bit patterns) instead of float32\n\n");
     printf("\t-s\tdata type the container was written with, [float | int], default float\n\n");
     printf("\t-g\tHIP device, default 0\n\n");
 }
@@ -302,12 +311,58 @@ static float *decode_binned(mrcz_ctx_t *c, const struct container *ct, const mrc
     return out;
 }
 
+/* the whole file with its `keep` top planes, written to fo piece by piece: 16 bytes per chunk header, then per chunk one pread of
+ * the kept payloads behind a copy of the header (thinned records) in a pinned buffer of the largest piece */
+static void extract_top(mrcz_ctx_t *c, const struct container *ct, int keep, int half, uint32_t batch, FILE *fo)
+{
+    const uint64_t chk = ct->chk, nch = (ct->nfl + chk - 1) / chk, esz = half ? 2 : 4;
+    uint64_t *at = (uint64_t *)malloc(8u * (size_t)nch), *kept = (uint64_t *)malloc(8u * (size_t)nch);
+    uint8_t *hdrs = (uint8_t *)malloc(16u * (size_t)nch);
+    if (!at || !kept || !hdrs) die("out of memory", NULL);
+    uint64_t off = MRCZ_FILE_HEADER_BYTES, biggest = 0, piece = 0;
+    for (uint64_t k = 0; k < nch; k++) { /* where every record's kept tail is: at[k], kept[k] bytes */
+        uint64_t skip = 0;
+        const uint64_t left = ct->nfl - k * chk;
+        pread_all(ct->fd, hdrs + 16 * k, 16, off, "truncated container (chunk header)");
+        if (mrcz_record_top_span(hdrs + 16 * k, (uint32_t)(left < chk ? left : chk), keep, &skip, &kept[k]) != MRCZ_OK) die("damaged chunk header", NULL);
+        at[k] = off + skip;
+        off = at[k] + kept[k];
+        piece += 16 + kept[k];
+        if ((k + 1) % batch == 0 || k + 1 == nch) { if (piece > biggest) biggest = piece; piece = 0; }
+    }
+    const uint64_t pw = (uint64_t)batch * chk; /* words of a full piece */
+    void *h_rec = NULL, *d_rec = NULL, *d_out = NULL, *h_out = NULL;
+    if (mrcz_host_malloc(c, &h_rec, biggest) || mrcz_host_malloc(c, &h_out, esz * pw) || mrcz_dev_malloc(c, &d_rec, biggest) || mrcz_dev_malloc(c, &d_out, esz * pw))
+        die("out of memory", c);
+    for (uint64_t k = 0; k < nch; k += batch) {
+        const uint64_t e = k + batch < nch ? k + batch : nch;
+        const uint64_t words = (e * chk < ct->nfl ? e * chk : ct->nfl) - k * chk;
+        uint64_t len = 0, consumed = 0;
+        for (uint64_t j = k; j < e; j++) {
+            memcpy((uint8_t *)h_rec + len, hdrs + 16 * j, 16);
+            pread_all(ct->fd, (uint8_t *)h_rec + len + 16, kept[j], at[j], "truncated container (payload)");
+            len += 16 + kept[j];
+        }
+        if (mrcz_copy_h2d(c, d_rec, h_rec, len) != MRCZ_OK) die("copy to the device", c);
+        if (mrcz_uncompress_top(c, d_rec, len, ct->nfl, ct->chk, k, e - k, keep, (half ? MRCZ_TOP_U16 : MRCZ_TOP_F32) | MRCZ_TOP_THINNED, d_out, &consumed) != MRCZ_OK)
+            die("top-planes decode", c);
+        if (consumed != len) die("top-planes decode: the records were not walked to their end", NULL);
+        if (mrcz_copy_d2h(c, h_out, d_out, esz * words) != MRCZ_OK) die("copy from the device", c);
+        if (fwrite(h_out, (size_t)esz, (size_t)words, fo) != (size_t)words) die("write", NULL);
+    }
+    mrcz_dev_free(c, d_out);
+    mrcz_dev_free(c, d_rec);
+    mrcz_host_free(c, h_out);
+    mrcz_host_free(c, h_rec);
+    free(at); free(kept); free(hdrs);
+}
+
 int main(int argc, char *argv[])
 {
-    const char *in = NULL, *outp = NULL, *wspec = NULL, *zspec = NULL, *bspec = NULL, *sspec = NULL, *fspec = NULL, *nspec = NULL, *dtype = "float";
-    int opt, device = 0;
+    const char *in = NULL, *outp = NULL, *wspec = NULL, *zspec = NULL, *bspec = NULL, *sspec = NULL, *fspec = NULL, *nspec = NULL, *pspec = NULL, *dtype = "float";
+    int opt, device = 0, half = 0, dtype_given = 0;
     if (argc < 2) { usage(argv[0]); return 255; }
-    while ((opt = getopt(argc, argv, "hi:o:w:z:B:S:F:N:s:g:")) != -1) {
+    while ((opt = getopt(argc, argv, "hi:o:w:z:B:S:F:N:P:Hs:g:")) != -1) {
         switch (opt) {
         case 'i': in = optarg; break;
         case 'o': outp = optarg; break;
@@ -317,14 +372,24 @@ int main(int argc, char *argv[])
         case 'S': sspec = optarg; break;
         case 'F': fspec = optarg; break;
         case 'N': nspec = optarg; break;
-        case 's': dtype = optarg; break;
+        case 'P': pspec = optarg; break;
+        case 'H': half = 1; break;
+        case 's': dtype = optarg; dtype_given = 1; break;
         case 'g': device = atoi(optarg); break;
         case 'h': usage(argv[0]); return 0;
         default: usage(argv[0]); return 255;
         }
     }
-    if (!in || !outp || !!wspec + !!zspec + !!bspec + !!nspec != 1) { usage(argv[0]); die("need -i, -o and one of -w, -z, -B, -N", NULL); }
+    if (!in || !outp || !!wspec + !!zspec + !!bspec + !!nspec + !!pspec != 1) { usage(argv[0]); die("need -i, -o and one of -w, -z, -B, -N, -P", NULL); }
     if (!bspec && (sspec || fspec)) die("-S and -F go with -B", NULL);
+    if (half && !pspec) die("-H goes with -P 2", NULL);
+    int keep = 0;
+    if (pspec) {
+        if ((pspec[0] != '2' && pspec[0] != '3') || pspec[1]) die("-P wants 2 or 3 (top byte planes kept)", NULL);
+        keep = pspec[0] - '0';
+        if (half && keep != 2) die("-H (16-bit words) goes with -P 2", NULL);
+        if (dtype_given && strcmp(dtype, "float") != 0) die("-P reads float containers only (-s int keeps its data in plane 0)", NULL);
+    }
     const int int_mode = strcmp(dtype, "int") == 0;
     if (!int_mode && strcmp(dtype, "float") != 0) die("-s must be float or int", NULL);
     uint64_t a = 0, b = 0;
@@ -340,7 +405,7 @@ int main(int argc, char *argv[])
             fill = strtof(fspec, &e);
             if (e == fspec || *e) die("-F wants a number", NULL);
         }
-    } else if (parse_pair(wspec ? wspec : zspec, &a, &b)) die(wspec ? "-w wants first:count" : "-z wants z0:z1", NULL);
+    } else if (!pspec && parse_pair(wspec ? wspec : zspec, &a, &b)) die(wspec ? "-w wants first:count" : "-z wants z0:z1", NULL);
 
     struct container ct;
     ct.fd = open(in, O_RDONLY);
@@ -357,6 +422,21 @@ int main(int argc, char *argv[])
         if (ct.ztypes[j] != 0 && ct.ztypes[j] != 2 && ct.ztypes[j] != 4) die("unknown byte stream compressor type in the file header", NULL);
 
     mrcz_ctx_t *c = NULL;
+    if (pspec) {
+        if (ct.nfl == 0) die("empty container", NULL);
+        const uint64_t nch = (ct.nfl + ct.chk - 1) / ct.chk;
+        const uint32_t batch = (uint32_t)(nch < 16 ? nch : 16);
+        if (mrcz_create(&c, device, batch) != MRCZ_OK) die("no usable HIP device (the codec has no CPU path)", NULL);
+        if (mrcz_set_ztypes(c, ct.ztypes) != MRCZ_OK) die("byte stream compressor types", c);
+        FILE *fo = fopen(outp, "wb");
+        if (!fo) die("cannot open the output file", NULL);
+        extract_top(c, &ct, keep, half, batch, fo);
+        if (fclose(fo) != 0) die("write", NULL);
+        printf("%" PRIu64 " words with their %d top byte planes (%s) written to %s\n", ct.nfl, keep, half ? "16-bit words" : "float32", outp);
+        close(ct.fd);
+        fflush(stdout);
+        _exit(0);
+    }
     if (nspec) {
         if (ct.nfl == 0) die("empty container", NULL);
         mrcz_box_geom_t v;

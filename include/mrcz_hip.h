@@ -356,6 +356,45 @@ int mrcz_digest_words_async(mrcz_ctx_t *ctx, const void *d_words, uint64_t nword
 int mrcz_digest_finish(mrcz_ctx_t *ctx, const mrcz_digest_t *d_acc, uint64_t first_chunk, uint64_t nchunks,
                        mrcz_digest_t *h_total);
 
+/*
+ * Top-planes decode: every word of a run of chunks at reduced precision, the low byte planes neither read nor decoded.  A chunk
+ * record is its 16-byte header (the four payload lengths) followed by the payloads of byte planes 0, 1, 2, 3 of the chunk's words;
+ * plane 3 is the sign and seven exponent bits of a float32, plane 2 its last exponent bit and top seven mantissa bits.  keep = 2
+ * or 3 is the number of top planes kept, mask(keep) = 0xFFFFFFFF << 8 (4 - keep).  For every word of the chunks asked for, file
+ * words 0 .. 255 included, the result is (what mrcz_uncompress_chunks returns) & mask(keep), exactly; nothing else is promised:
+ *   - keep = 2 is the bfloat16 TRUNCATION of the float32 (toward zero; torch's .to(bfloat16) rounds to nearest): the relative
+ *     error is below 2^-7 (keep 2) or 2^-15 (keep 3) for normal numbers;
+ *   - NaN payload bits of the dropped planes are lost: a NaN whose only set mantissa bits were there becomes +-Inf;
+ *   - the 256 header words are truncated like the rest (two planes cannot restore them): read the MRC header by range decode;
+ *   - "-s int" containers keep their data in plane 0: there is no int_mode.  mrcz_set_ztypes applies to the kept planes.
+ *   mrcz_record_top_span  (host arithmetic, the checks of mrcz_record_size on all four lengths) for the record of a chunk of n
+ *                         floats whose 16-byte header is h_header16: skip = offset inside the record of the first kept payload
+ *                         (16 + the lengths of the dropped planes), bytes = total length of the kept payloads.  MRCZ_EINVAL: a
+ *                         NULL pointer, keep outside {2, 3}; MRCZ_EFORMAT: lengths no record of such a chunk can have.
+ *   thinned record        the record's 16-byte header, unchanged, directly followed by its kept payloads: what a reader that
+ *                         fetches [record + skip, record + skip + bytes) behind the header holds.
+ *   mrcz_uncompress_top   d_records/len = the records of chunks [first_chunk, first_chunk + nchunks) of a file of nfloats_file
+ *                         words: ordinary records (the dropped payloads are stepped over by their lengths, never read) or, with
+ *                         MRCZ_TOP_THINNED, thinned records.  The chunks are decoded in runs of up to max_batch_chunks and their
+ *                         words written contiguously to d_out (16-byte aligned): min(nchunks * chk, nfloats_file - first_chunk *
+ *                         chk) elements, uint32 (MRCZ_TOP_F32: the dropped planes' bytes zero) or uint16 = word >> 16
+ *                         (MRCZ_TOP_U16, keep 2 only: the bfloat16 bit pattern).  consumed (optional) = bytes of d_records
+ *                         walked.  Synchronous; mrcz_uncompress_top_async enqueues on the compute stream, h_result3 as
+ *                         mrcz_uncompress_chunks_async.
+ * MRCZ_EINVAL: keep outside {2, 3}, MRCZ_TOP_U16 with keep 3, unknown flag bits, a NULL or misaligned pointer (d_records may be
+ * NULL when nchunks == 0), first_chunk + nchunks past the file; MRCZ_EFORMAT: chk of 0 or above MRCZ_CHUNK_FLOATS, a header
+ * length no record can have, malformed kept streams, records that end early (never read past len).  A malformed DROPPED payload
+ * is by design no error: it is never looked at.  nchunks == 0 is MRCZ_OK and touches nothing.
+ */
+#define MRCZ_TOP_F32 0
+#define MRCZ_TOP_U16 1
+#define MRCZ_TOP_THINNED 4
+int mrcz_record_top_span(const void *h_header16, uint32_t n, int keep, uint64_t *skip, uint64_t *bytes);
+int mrcz_uncompress_top(mrcz_ctx_t *ctx, const void *d_records, uint64_t len, uint64_t nfloats_file, uint32_t chk,
+                        uint64_t first_chunk, uint64_t nchunks, int keep, int flags, void *d_out, uint64_t *consumed);
+int mrcz_uncompress_top_async(mrcz_ctx_t *ctx, const void *d_records, uint64_t len, uint64_t nfloats_file, uint32_t chk,
+                              uint64_t first_chunk, uint64_t nchunks, int keep, int flags, void *d_out, uint64_t *h_result3);
+
 /* apply_mask alone on device (the erasebytes restatement used by the GPU-side verification tools,
  * src/tool/erasebytes.c:109-134): words [256, nwords) of a file &= mask(bits).  In place. */
 int mrcz_erase_bits(mrcz_ctx_t *ctx, void *d_words, uint64_t nwords, uint64_t first_word_index, int bits);
