@@ -354,7 +354,7 @@ static int ensure_planes(mrcz_ctx *ctx)
 
 /* One half ("lane") of a compress batch: chunks [c_first, c_first + nb) of the batch, whose workspace rows start at
  * stream s0 = 4 * (chunks of the batch before this lane).  phase 0 = everything up to the sizes (summary ... pair
- * offsets), phase 1 = layout in the output, phase 2 = zero + headers + emit.  The kernels index the workspace by the
+ * offsets), phase 1 = layout in the output + chunk headers, phase 2 = boundary words + emit.  The kernels index the workspace by the
  * lane-local stream number, so a lane is just a set of offset base pointers. */
 static int compress_lane(mrcz_ctx *ctx, hipStream_t lstream, int phase, int slot, uint32_t s0, const uint32_t *bin, uint64_t bfl,
                          uint32_t nb, uint32_t mask, uint32_t fstart, uint8_t *out, Xform xf, AbsErr ae)
@@ -395,11 +395,10 @@ static int compress_lane(mrcz_ctx *ctx, hipStream_t lstream, int phase, int slot
         LAUNCH("k_pair_bits", k_pair_bits, dim3(SPS, ns), dim3(64), sinfo, lay, pairhist, blkcode, tinfo, pairbits);
         LAUNCH("k_pair_offsets", k_pair_offsets, dim3(ns), dim3(64), sinfo, lay, tinfo, pairbits, pairoff);
     } else if (phase == 1) {
-        LAUNCH("k_container", k_container, dim3(1), dim3(256), sinfo, nb, out, ctx->result, 0, slot);
+        LAUNCH("k_container", k_container, dim3(1), dim3(256), sinfo, nb, out, ctx->result);
     } else {
-        LAUNCH("k_zero_records", k_zero_records, dim3(2048), dim3(256), out, ctx->result, slot);
-        LAUNCH("k_container", k_container, dim3(1), dim3(256), sinfo, nb, out, ctx->result, 1, slot);
-        LAUNCH("k_emit", k_emit, dim3(SPS, nb, 4), dim3(64), planes, bfl, tinfo, sinfo, lay, blkstart, blkcode, pairoff, out);
+        LAUNCH("k_clear_boundaries", k_clear_boundaries, dim3(MAXBLK + 1, ns), dim3(64), sinfo, lay, meta, pairoff, out);
+        LAUNCH("k_emit", k_emit, dim3(SPS, nb, 4), dim3(64), planes, bfl, tinfo, sinfo, lay, blkstart, blkcode, pairoff, out, ctx->result);
         LAUNCH("k_emit_headers", k_emit_headers, dim3(MAXBLK + 1, ns), dim3(64), sinfo, lay, meta, blkhdr, blkstart, out);
     }
     return MRCZ_OK;
@@ -1059,6 +1058,16 @@ extern "C" int mrcz_debug_candidates(mrcz_ctx_t *ctx, uint64_t out[2])
     if (hipMemcpy(nc, ctx->ncand, ns * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return MRCZ_EHIP;
     for (uint32_t s = 0; s < ns; s++) out[1] += nc[s];
     return MRCZ_OK;
+}
+
+/* tile parts of the last compress call whose bits did not fit k_emit's staging buffer and went out in two halves (the
+ * decoders clear only the first eight result words) */
+extern "C" int64_t mrcz_debug_emit_splits(mrcz_ctx_t *ctx)
+{
+    if (!ctx) return -1;
+    uint64_t v = 0;
+    if (hipSetDevice(ctx->device) != hipSuccess || hipMemcpy(&v, ctx->result + 8, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return (int64_t)v;
 }
 
 extern "C" int64_t mrcz_debug_fallbacks(const mrcz_ctx_t *ctx) { return ctx ? (int64_t)ctx->last_fallbacks : -1; }

@@ -19,7 +19,8 @@
  *   k_stream_layout  small     : stored/static/dynamic choice, block bit offsets, RAW test
  *   k_pair_bits/_off small     : bit offset of every pair
  *   k_container      small     : payload offsets + 16-byte chunk headers
- *   k_emit           N B x 4 read, Z B written : Huffman/stored/raw bit packing
+ *   k_clear_boundaries small   : zero the few words in which two writers meet (the output is not zero-filled)
+ *   k_emit           N B x 4 read, Z B written : Huffman/stored/raw bit packing, whole words
  *   k_emit_headers   small     : block headers, END_BLOCK codes, sync markers
  * No MFMA anywhere: the path is byte/bit manipulation bound by HBM and LDS.
  */
@@ -749,32 +750,12 @@ __global__ __launch_bounds__(64) void k_pair_offsets(const StreamInfo *__restric
 /* ======================================================================================
  * container layout: payload offsets + the 16-byte chunk headers (workers.c:837-842, zip.c:381-391)
  * ==================================================================================== */
-/* zero the records one lane of a batch is about to emit, bytes [result[8 + slot], result[12 + slot]) of the output:
- * the emit kernels OR their bit strings into it.  Exactly that range: the bytes before it belong to the previous
- * lane or batch and the bytes after it to the next one, which may already be written (lanes run on two streams).
- * Clearing what is produced instead of the whole mrcz_records_bound() halves the bytes written up front. */
-__global__ __launch_bounds__(256) void k_zero_records(uint8_t *__restrict__ out, const uint64_t *__restrict__ result, int slot)
-{
-    uint8_t *b = out + result[8 + slot], *e = out + result[12 + slot];
-    uint8_t *ba = reinterpret_cast<uint8_t *>(((uintptr_t)b + 15u) & ~(uintptr_t)15u);
-    uint8_t *ea = reinterpret_cast<uint8_t *>((uintptr_t)e & ~(uintptr_t)15u);
-    if (ba > e) ba = e;
-    if (ea < ba) ea = ba;
-    if (blockIdx.x == 0 && threadIdx.x < 16u && b + threadIdx.x < ba) b[threadIdx.x] = 0;       /* head */
-    if (blockIdx.x == 1 && threadIdx.x < 16u && ea + threadIdx.x < e) ea[threadIdx.x] = 0;      /* tail */
-    uint4 *p = reinterpret_cast<uint4 *>(ba);
-    const uint64_t n = (uint64_t)(ea - ba) >> 4;
-    const uint4 z = make_uint4(0, 0, 0, 0);
-    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) p[i] = z;
-}
-
 __global__ __launch_bounds__(256) void k_container(StreamInfo *__restrict__ sinfo, uint32_t nchunks, uint8_t *__restrict__ out,
-                                                   uint64_t *__restrict__ result /* [0] running byte offset, [1..4] per-plane zfsz,
-                                                                                    [8 + slot] / [12 + slot] where this lane's records start / end */,
-                                                   int write_headers, int slot)
+                                                   uint64_t *__restrict__ result /* [0] running byte offset, [1..4] per-plane zfsz */)
 {
-    /* called twice per lane of a batch: write_headers = 0 lays the lane out (payload offsets, running offset), then
-     * its records are zeroed, then write_headers = 1 stores the 16-byte chunk headers */
+    /* once per lane of a batch, in lane (= file) order: payload offsets, the running offset and the 16-byte chunk headers.
+     * The headers are byte stores, and nothing else ever writes a header byte (k_clear_boundaries and the emit kernels stay
+     * inside the payloads, byte for byte), so they need no ordering against the emit kernels of this or another lane. */
     /* one thread per chunk of the batch (<= 128 chunks, records < 4 GiB) */
     __shared__ SegPair wsum[4];
     const uint32_t c = threadIdx.x;
@@ -789,30 +770,82 @@ __global__ __launch_bounds__(256) void k_container(StreamInfo *__restrict__ sinf
         }
         v.sum = 16u + len[0] + len[1] + len[2] + len[3];
     }
-    const uint64_t base = write_headers ? result[8 + slot] : result[0];
+    const uint64_t base = result[0];
     const SegPair pre = block_excl_scan(v, wsum);
     if (c < nchunks) {
         const uint64_t off = base + pre.sum;
         uint64_t p = off + 16;
         for (int j = 0; j < 4; j++) {
-            if (write_headers) {
-                uint8_t *h = out + off + 4u * j;   /* pack_header, zip.c:381-391 */
-                h[0] = (uint8_t)(len[j] & 0xff);
-                h[1] = (uint8_t)((len[j] >> 8) & 0xff);
-                h[2] = (uint8_t)((len[j] >> 16) & 0xff);
-                h[3] = (uint8_t)(((len[j] >> 24) & 0x7f) | (raw[j] << 7));
-            } else {
-                sinfo[4 * c + j].payoff = p;
-                atomicAdd((unsigned long long *)&result[1 + j], (unsigned long long)len[j] + 4ull);
-            }
+            uint8_t *h = out + off + 4u * j;   /* pack_header, zip.c:381-391 */
+            h[0] = (uint8_t)(len[j] & 0xff);
+            h[1] = (uint8_t)((len[j] >> 8) & 0xff);
+            h[2] = (uint8_t)((len[j] >> 16) & 0xff);
+            h[3] = (uint8_t)(((len[j] >> 24) & 0x7f) | (raw[j] << 7));
+            sinfo[4 * c + j].payoff = p;
+            atomicAdd((unsigned long long *)&result[1 + j], (unsigned long long)len[j] + 4ull);
             p += len[j];
         }
     }
     __syncthreads();
-    if (!write_headers && c + 1 == nchunks) {
-        result[8 + slot] = base;
-        result[12 + slot] = base + pre.sum + v.sum;
-        result[0] = base + pre.sum + v.sum;
+    if (c + 1 == nchunks) result[0] = base + pre.sum + v.sum;
+}
+
+/* ======================================================================================
+ * boundary words
+ * ==================================================================================== */
+/* The output is not zeroed.  Every dword of a payload is either stored in full exactly once (the inside of a wave's bit
+ * string, the inside of a stored block, a RAW plane) or it is a BOUNDARY word, in which two writers meet and into which
+ * the emit kernels OR their bits.  The boundary words are few and the layout knows them all:
+ *   - the word in which a pair starts, and the word before that bit (where the writer in front of it ends);
+ *   - a block's header, from its first bit to its first data bit (type bits, dynamic header, or pad + LEN/NLEN);
+ *   - a coded block's END_BLOCK code;
+ *   - the stream's tail: the empty stored block of the full flush.
+ * k_clear_boundaries zeroes them, ordered on the lane's stream before k_emit and k_emit_headers.  It may clear more than
+ * is ORed later (a pair start that falls on a word boundary, a word another wave stores in full): every clear comes
+ * before every write.  What it must not touch is a byte outside the stream's own payload: the neighbouring payload may
+ * be a RAW plane, a chunk header, or another lane's or batch's records, written on another stream.  A word that straddles
+ * the payload's first or last byte is therefore cleared byte by byte. */
+__device__ __forceinline__ void clear_payload_bits(uint8_t *out, uint64_t pb, uint64_t pe /* payload bytes [pb, pe) */, uint32_t lo,
+                                                   uint32_t hi /* stream bits [lo, hi) */, int lane)
+{
+    if (hi <= lo) return;
+    const uint64_t w0 = (pb * 8ull + lo) >> 5, w1 = (pb * 8ull + hi - 1u) >> 5;
+    for (uint64_t w = w0 + (uint64_t)lane; w <= w1; w += 64u) {
+        const uint64_t b = 4ull * w;
+        if (b >= pb && b + 4u <= pe) reinterpret_cast<uint32_t *>(out)[w] = 0u;
+        else
+            for (uint64_t j = b; j < b + 4u; j++)
+                if (j >= pb && j < pe) out[j] = 0;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_clear_boundaries(const StreamInfo *__restrict__ sinfo, const BlkLay *__restrict__ lay,
+                                                         const BlkMeta *__restrict__ meta, const uint32_t *__restrict__ pairoff,
+                                                         uint8_t *__restrict__ out)
+{
+    const uint32_t b = blockIdx.x, s = blockIdx.y;
+    const StreamInfo si = sinfo[s];
+    if (si.raw) return; /* a RAW plane is plain byte stores */
+    const int lane = lane_id();
+    const uint64_t pb = si.payoff, pe = si.payoff + si.paylen;
+    /* pair starts, spread over the workgroups of the stream */
+    const uint32_t npair = si.nseg ? si.nseg + si.nsym / BLK_SYMS : 0u;
+    for (uint32_t i = b * 64u + (uint32_t)lane; i < npair; i += gridDim.x * 64u) {
+        const uint32_t p = pairoff[(size_t)s * MAXPAIR + i];
+        clear_payload_bits(out, pb, pe, p ? p - 1u : 0u, p + 1u, 0);
+    }
+    if (b > si.nblk) return;
+    if (b == si.nblk) { /* 000, pad to byte, 00 00 FF FF */
+        clear_payload_bits(out, pb, pe, si.zbits, 8u * si.paylen, lane);
+        return;
+    }
+    const BlkLay L = lay[(size_t)s * MAXBLK + b];
+    clear_payload_bits(out, pb, pe, L.bitpos, L.databit, lane);
+    if (L.btype != 0u) {
+        int l = 0;
+        if (L.btype == 1u) (void)static_lcode(256, &l);
+        else l = (int)(meta[(size_t)s * MAXBLK + b].eob >> 16);
+        clear_payload_bits(out, pb, pe, L.endbit - (uint32_t)l, L.endbit, lane);
     }
 }
 
@@ -823,8 +856,8 @@ constexpr int STAGE_WORDS = 1280; /* 5 KiB per wave.  A tile's 4096 symbols are 
                                     * eight bits a symbol or it would have been stored: 5 KiB hold nearly every tile, and one that does not fit is
                                     * emitted in two halves.  The 3 KiB are what lets more emit waves sit beside the other lane's Huffman trees. */
 
-/* OR `nbits` (<= 32) bits of `val` into the bit string at absolute bit position `pos` of a zeroed
- * device buffer (32-bit atomics: neighbouring writers share boundary words) */
+/* OR `nbits` (<= 32) bits of `val` into the bit string at absolute bit position `pos` of the output, into words that
+ * k_clear_boundaries has zeroed (32-bit atomics: neighbouring writers share boundary words) */
 __device__ __forceinline__ void global_or_bits(uint32_t *out32, uint64_t pos, uint32_t val, int nbits)
 {
     if (nbits <= 0) return;
@@ -943,7 +976,8 @@ __device__ __forceinline__ void quarter_emit(LanePacker &pk, const uint32_t *lut
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))) void k_emit(const uint8_t *__restrict__ planes, uint64_t nfloats, const TileInfo *__restrict__ tinfo,
                                               const StreamInfo *__restrict__ sinfo, const BlkLay *__restrict__ lay,
                                               const uint32_t *__restrict__ blkstart, const uint32_t *__restrict__ blkcode,
-                                              const uint32_t *__restrict__ pairoff, uint8_t *__restrict__ out)
+                                              const uint32_t *__restrict__ pairoff, uint8_t *__restrict__ out,
+                                              uint64_t *__restrict__ result /* [8] += tile parts cut in two (mrcz_debug_emit_splits) */)
 {
     /* one wave = one (segment, plane): no workgroup barriers, light planes retire early.  The lane's 64 plane bytes stay in
      * registers for both passes: an LDS copy of the tile costs 5 KB per wave and with it a third of the occupancy, and this
@@ -968,6 +1002,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))
     int mode = -1;           /* 0 stored, 1 static, 2 dynamic */
     uint32_t blkEnd = 0;     /* position where the current block ends */
     uint32_t dbits = 0;      /* distance-code bits per match (1 dynamic, 5 static) */
+    /* The bits a wave writes into one coded block are one bit string (its pair), produced a tile part at a time.  The
+     * dword in which one part ends and the next begins is carried from part to part and stored once it is full; only
+     * the pair's first word (when the pair starts inside it) and its last, unfinished word meet another writer and
+     * are ORed into the output, into words k_clear_boundaries has zeroed. */
+    uint32_t carry = 0;      /* this wave's bits of the dword that holds bit paybit + cur */
+    bool have_carry = false; /* (then paybit + cur is not a multiple of 32) */
+    bool carry_shared = false; /* the carried dword's low bits belong to the writer in front of the pair */
 
     for (int ti = 0; ti < TILES_PER_SEG; ti++) {
         const uint32_t t0 = g * SEG + ti * TILE;
@@ -1007,6 +1048,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))
         int cap = len; /* the part ends here at the latest */
         for (int part = 0; part < 16 && pos0 < len; part++) {
             if (mode < 0 || t0 + (uint32_t)pos0 >= blkEnd) {
+                if (have_carry) { /* the pair ends inside a word */
+                    if (lane == 0 && carry) atomicOr(&out32[(paybit + cur) >> 5], carry);
+                    have_carry = false;
+                }
                 if (mode >= 0) curBlk++;
                 const BlkLay L = blay[curBlk];
                 mode = (int)L.btype;
@@ -1036,7 +1081,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))
             if (mode == 0) {
                 /* STORED block: plane bytes [pos0, pos1) go out verbatim at a byte-aligned address.  The wave assembles
                  * aligned output dwords from the plane in HBM (the tile was just read: cache hits; stored blocks are only the
-                 * first and last block of an incompressible plane); a partial first / last dword is merged with atomicOr. */
+                 * first and last block of an incompressible plane); a partial first / last dword goes out byte by byte. */
                 const uint32_t nbytes = (uint32_t)(pos1 - pos0);
                 const uint64_t dg = si.payoff + (cur >> 3);       /* cur is a multiple of 8 here */
                 const uint32_t mis = (uint32_t)(dg & 3u);
@@ -1053,7 +1098,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))
                         else full = false;
                     }
                     if (full) out32[w0 + k] = v;
-                    else if (v) atomicOr(&out32[w0 + k], v);
+                    else {
+#pragma unroll
+                        for (int j = 0; j < 4; j++) {
+                            const int rel = (int)(4u * k + (uint32_t)j) - (int)mis;
+                            if (rel >= 0 && rel < (int)nbytes) out[4u * (w0 + k) + (uint32_t)j] = (uint8_t)(v >> (8 * j));
+                        }
+                    }
                 }
                 cur += 8u * nbytes;
                 pos0 = pos1; cap = len;
@@ -1096,9 +1147,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))
                 const uint32_t nwords = (lead + tot + 31u) >> 5;
                 if (nwords > (uint32_t)STAGE_WORDS) { /* (wave-uniform; one lane's 64 symbols always fit) */
                     cap = pos0 + ((((pos1 - pos0) >> 1) + 63) & ~63);
+                    if (lane == 0) atomicAdd((unsigned long long *)&result[8], 1ull);
                     continue;
                 }
+                /* word 0 holds bits of the writer in front of this pair: the pair starts inside it, and it is either this
+                 * part's own first word or a carried word that began that way */
+                const bool first_shared = lead != 0u && (!have_carry || carry_shared);
                 for (uint32_t i = lane; i < nwords; i += 64) stage[i] = 0;
+                if (have_carry && lane == 0) stage[0] = carry; /* (have_carry implies lead != 0: the first lane ORs into it) */
                 __builtin_amdgcn_wave_barrier();
                 LanePacker pk;
                 packer_init(pk, stage, lead + lofs);
@@ -1112,17 +1168,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))
                 packer_finish(pk);
                 __builtin_amdgcn_wave_barrier();
                 const uint64_t w0 = gbit >> 5;
-                for (uint32_t i = lane; i < nwords; i += 64) {
+                const bool open_end = ((lead + tot) & 31u) != 0u; /* the last word is unfinished: carried, not written */
+                const uint32_t nout = open_end ? nwords - 1u : nwords;
+                for (uint32_t i = lane; i < nout; i += 64) {
                     const uint32_t v = stage[i];
-                    if (i == 0 || i == nwords - 1) { if (v) atomicOr(&out32[w0 + i], v); }
+                    if (i == 0 && first_shared) { if (v) atomicOr(&out32[w0], v); }
                     else out32[w0 + i] = v;
                 }
+                if (open_end) {
+                    carry = (uint32_t)__builtin_amdgcn_readfirstlane((int)stage[nwords - 1u]);
+                    carry_shared = nwords == 1u && first_shared;
+                }
+                have_carry = open_end;
                 __builtin_amdgcn_wave_barrier();
                 cur += tot;
             }
             pos0 = pos1; cap = len;
         }
     }
+    if (have_carry && lane == 0 && carry) atomicOr(&out32[(paybit + cur) >> 5], carry); /* the wave's last pair ends inside a word */
 }
 
 /* ======================================================================================

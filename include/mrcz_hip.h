@@ -447,6 +447,10 @@ int mrcz_debug_blocks(mrcz_ctx_t *ctx, uint32_t stream, mrcz_block_info_t *block
 int64_t mrcz_debug_fallbacks(const mrcz_ctx_t *ctx);
 int64_t mrcz_debug_chain_fallbacks(mrcz_ctx_t *ctx);
 
+/* Inspection (tests): tile parts of the last compress call whose coded bits exceeded the emit kernel's
+ * staging buffer and were emitted in two halves (-1 on error). */
+int64_t mrcz_debug_emit_splits(mrcz_ctx_t *ctx);
+
 /* Inspection (profiling): enable/disable the in-kernel phase counters of the parallel inflate and
  * (if out != NULL) read the 20 counters of `stream` from the last call (shader clocks of thread 0):
  * [0] header+tables [1] staging [2] exit functions [3] composition [4] count walk [5] scans

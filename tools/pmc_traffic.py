@@ -34,7 +34,7 @@ out = {"source": f"rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE 
                  "streaming loads (fetch_factor 2), as reported for the others",
        "passes": passes, "kernels": {}}
 COMPRESS = {"k_tile_summary", "k_stream_scan", "k_histogram", "k_block_reduce", "k_block_index", "k_huffman", "k_huffman_hdr", "k_stream_layout", "k_pair_bits",
-            "k_pair_offsets", "k_container", "k_zero_records", "k_emit", "k_emit_headers"}
+            "k_pair_offsets", "k_container", "k_zero_records", "k_clear_boundaries", "k_emit", "k_emit_headers"}
 tot = {"compress": 0, "decompress": 0}
 for k in sorted(set(fetch) | set(write)):
     if not k.startswith("k_"):
