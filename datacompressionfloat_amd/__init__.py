@@ -12,6 +12,7 @@ from .codec import (  # noqa: F401
     MRC_HEADER_BYTES,
     MrcZipCodec,
     MrczError,
+    choose,
     crc32_combine,
     format_sidecar,
     pack_file_header,

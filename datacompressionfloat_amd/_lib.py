@@ -38,6 +38,7 @@ class MrczDigest(ctypes.Structure):
 
 DIGEST_NONE, DIGEST_MASK, DIGEST_INT8, DIGEST_ABS = 0, 1, 2, 3  # MRCZ_DIGEST_*
 TOP_F32, TOP_U16, TOP_THINNED = 0, 1, 4                         # MRCZ_TOP_*
+PROBE_MASK, PROBE_ABS, PROBE_INT8 = 0, 1, 2                     # MRCZ_PROBE_*
 
 
 def load():
@@ -92,6 +93,9 @@ def load():
     lib.mrcz_uncompress_compare.argtypes = [vp, vp, u64, u64, u32, u64, u64, vp, ctypes.c_double, ctypes.c_double, i32, vp]
     lib.mrcz_compare_finish.restype = i32
     lib.mrcz_compare_finish.argtypes = [vp, vp, u64, u64, ctypes.POINTER(MrczCompare)]
+    lib.mrcz_probe_chunks.restype = i32
+    lib.mrcz_probe_chunks.argtypes = [vp, vp, u64, u64, i32, i32, ctypes.c_float, ctypes.c_double, ctypes.c_double, vp, ctypes.POINTER(u64),
+                                      ctypes.POINTER(u64)]
     lib.mrcz_crc32_combine.restype = u32
     lib.mrcz_crc32_combine.argtypes = [u32, u32, u64]
     lib.mrcz_uncompress_digest.restype = i32
@@ -140,6 +144,7 @@ EXPORTS = [
     "mrcz_bin_chunks", "mrcz_uncompress_binned", "mrcz_binned_finish",
     "mrcz_compress_chunks_abs", "mrcz_compress_chunks_abs_async", "mrcz_erase_abs",
     "mrcz_uncompress_compare", "mrcz_compare_finish",
+    "mrcz_probe_chunks", "mrcz_probe_chunks_async",
     "mrcz_crc32_combine", "mrcz_uncompress_digest", "mrcz_digest_words", "mrcz_digest_words_async", "mrcz_digest_finish",
     "mrcz_record_top_span", "mrcz_uncompress_top", "mrcz_uncompress_top_async",
 ]

@@ -14,8 +14,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (DIGEST_ABS, DIGEST_INT8, DIGEST_MASK, DIGEST_NONE, TOP_F32, TOP_THINNED, TOP_U16, MrczBinGeom, MrczBoxGeom, MrczCompare,
-                   MrczDigest)
+from ._lib import (DIGEST_ABS, DIGEST_INT8, DIGEST_MASK, DIGEST_NONE, PROBE_ABS, PROBE_INT8, PROBE_MASK, TOP_F32, TOP_THINNED, TOP_U16,
+                   MrczBinGeom, MrczBoxGeom, MrczCompare, MrczDigest)
 
 CHUNK_FLOATS = 6 * 1048576  # src/include/constant.h:25
 FILE_HEADER_BYTES = 17      # src/core/common.c:137-148
@@ -107,6 +107,23 @@ def parse_sidecar(text) -> dict:
             raise MrczError(f"damaged digest sidecar: chunk line {c}")
         crcs.append(int(p[1], 16))
     return {"words": nfl, "chunk": chk, "chunks": nch, "mode": t[7], "file": int(f[1], 16), "crcs": crcs}
+
+
+def choose(rows, max_err=None, max_rmse=None, min_psnr=None):
+    """the row of MrcZipCodec.sweep with the smallest container_bytes among those that meet every constraint given (max_err >=
+    row max_err, max_rmse >= row rmse, min_psnr <= row psnr_db); the earlier row on a tie; None when no row meets them.  Pure
+    host arithmetic."""
+    best = None
+    for r in rows:
+        if max_err is not None and not r["max_err"] <= max_err:
+            continue
+        if max_rmse is not None and not r["rmse"] <= max_rmse:
+            continue
+        if min_psnr is not None and not r["psnr_db"] >= min_psnr:
+            continue
+        if best is None or r["container_bytes"] < best["container_bytes"]:
+            best = r
+    return best
 
 
 def read_thinned_records(f, nfl: int, chk: int, keep: int, first_chunk: int = 0, nchunks: int = None, start: int = None):
@@ -457,6 +474,104 @@ class MrcZipCodec:
             return t
         raw = acc.cpu().numpy().tobytes()
         return t, [self._compare_dict(MrczCompare.from_buffer_copy(raw[c * rsz: (c + 1) * rsz])) for c in range(nch)]
+
+    # ---- probe: the size and the error of a compress setting, nothing written ----
+    def probe_device(self, words: torch.Tensor, bits: int = 0, first_chunk: int = 0, int_mode: bool = False, abs_err=None, acc: torch.Tensor = None,
+                     err_abs=None, err_rel=None):
+        """what compress_device(words, bits, first_chunk, int_mode=..., abs_err=...) would write and how well it would decode,
+        without writing it (mrcz_probe_chunks): `words` as there, the same argument checks.  Returns (record bytes, plane_bytes[4],
+        acc): the first two are exactly what compress_device returns as len(records) and plane_bytes; record first_chunk + i of
+        `acc` (a cuda uint8 tensor of (first_chunk + chunks of words) * sizeof(MrczCompare) bytes, allocated when None, no zeroing
+        needed) is the MrczCompare of chunk i as uncompress_compare_device would assign it for that container against `words`,
+        with the bounds err_abs / err_rel counted in n_over_abs / n_over_rel (None: off).  Then compare_finish_device."""
+        assert words.is_cuda and words.is_contiguous() and words.element_size() == 4
+        if abs_err is not None:
+            if bits != 0 or int_mode:
+                raise MrczError("abs_err excludes bits != 0 and the int mode")
+            abs_err = abs_bound(abs_err)
+        n = words.numel()
+        nch = first_chunk + (n + CHUNK_FLOATS - 1) // CHUNK_FLOATS
+        rsz = ctypes.sizeof(MrczCompare)
+        if acc is None:
+            acc = torch.empty(max(nch, 1) * rsz, dtype=torch.uint8, device=words.device)
+        assert acc.is_cuda and acc.dtype == torch.uint8 and acc.is_contiguous() and acc.numel() >= nch * rsz
+        torch.cuda.current_stream(words.device).synchronize()
+        olen = ctypes.c_uint64()
+        planes = (ctypes.c_uint64 * 4)()
+        xform = PROBE_INT8 if int_mode else PROBE_ABS if abs_err is not None else PROBE_MASK
+        rc = _LIB.mrcz_probe_chunks(self._ctx, words.data_ptr(), n, first_chunk, xform, 0 if int_mode else bits, abs_err or 0.0,
+                                    -1.0 if err_abs is None else float(err_abs), -1.0 if err_rel is None else float(err_rel), acc.data_ptr(),
+                                    ctypes.byref(olen), planes)
+        if rc != 0:
+            raise self._err("mrcz_probe_chunks", rc)
+        return int(olen.value), [int(p) for p in planes], acc
+
+    def sweep(self, original, settings=None, per_chunk: bool = False):
+        """the table a lossy setting is chosen from: for every setting the size of the container it would give and the error of
+        what that container would decode to, from one read of `original` (bytes, a path, or a cuda tensor of the file's words)
+        and without writing a container.  settings = a list of ("bits", b), ("abs", eps) and ("int",); default all 33 mask levels.
+        A host original is read and uploaded once, in pieces of at most max_batch_chunks chunks, and every setting is probed on
+        each resident piece (probe_device), so a file larger than device memory streams through.  Returns one dict per setting:
+        setting, container_bytes (17 + record bytes; 0 for a file of fewer than 4 bytes, where zip_bytes returns b""), ratio (file
+        bytes / container bytes), plane_bytes, the MrczCompare fields of the file, and mean_err, rmse, psnr_db as verify derives
+        them.  per_chunk: each dict also holds "chunks", the list of the chunks' MrczCompare dicts."""
+        if settings is None:
+            settings = [("bits", b) for b in range(33)]
+        kws = []
+        for st in settings:
+            st = tuple(st)
+            if len(st) == 2 and st[0] == "bits" and 0 <= int(st[1]) <= 32:
+                kws.append(dict(bits=int(st[1])))
+            elif len(st) == 2 and st[0] == "abs":
+                kws.append(dict(abs_err=abs_bound(st[1])))
+            elif st == ("int",):
+                kws.append(dict(int_mode=True))
+            else:
+                raise MrczError(f"setting {st!r}: want ('bits', 0..32), ('abs', eps) or ('int',)")
+        dev = isinstance(original, torch.Tensor)
+        if dev:
+            assert original.is_cuda and original.is_contiguous() and original.element_size() == 4
+            src, fsz = None, original.numel() * 4
+        else:
+            src = io.BytesIO(original) if isinstance(original, (bytes, bytearray, memoryview)) else open(os.fspath(original), "rb")
+            fsz = src.seek(0, os.SEEK_END)
+        try:
+            nfl = fsz // 4
+            nch = (nfl + CHUNK_FLOATS - 1) // CHUNK_FLOATS
+            rsz = ctypes.sizeof(MrczCompare)
+            accs = [torch.empty(max(nch, 1) * rsz, dtype=torch.uint8, device=self.device) for _ in kws]
+            size = [0] * len(kws)
+            planes = [[0, 0, 0, 0] for _ in kws]
+            step = max(int(self.max_batch_chunks), 1)
+            for k in range(0, nch, step):
+                w0, w1 = k * CHUNK_FLOATS, min((k + step) * CHUNK_FLOATS, nfl)
+                if dev:
+                    piece = original.reshape(-1)[w0:w1]
+                else:
+                    src.seek(4 * w0)
+                    piece = torch.frombuffer(bytearray(src.read(4 * (w1 - w0))), dtype=torch.int32).to(self.device)
+                for i, kw in enumerate(kws):
+                    n, pl, _ = self.probe_device(piece, first_chunk=k, acc=accs[i], **kw)
+                    size[i] += n
+                    planes[i] = [a + b for a, b in zip(planes[i], pl)]
+                del piece
+            rows = []
+            for i, st in enumerate(settings):
+                t = self._compare_dict(self.compare_finish_device(accs[i], 0, nch))
+                n = t["n_finite"]
+                t["mean_err"] = t["sum_err"] / n if n else 0.0
+                t["rmse"] = float(np.sqrt(t["sum_err2"] / n)) if n else 0.0
+                t["psnr_db"] = float("inf") if t["rmse"] == 0 else float(20.0 * np.log10((t["orig_max"] - t["orig_min"]) / t["rmse"]))
+                cb = FILE_HEADER_BYTES + size[i] if nfl else 0
+                row = {"setting": tuple(st), "container_bytes": cb, "ratio": fsz / cb if cb else 0.0, "plane_bytes": planes[i], **t}
+                if per_chunk:
+                    raw = accs[i].cpu().numpy().tobytes()
+                    row["chunks"] = [self._compare_dict(MrczCompare.from_buffer_copy(raw[c * rsz: (c + 1) * rsz])) for c in range(nch)]
+                rows.append(row)
+        finally:
+            if src is not None:
+                src.close()
+        return rows
 
     def uncompress_digest_device(self, records: torch.Tensor, nfloats_file: int, acc: torch.Tensor, first_chunk: int = 0, nchunks: int = None,
                                  chk: int = CHUNK_FLOATS, int_mode: bool = False):

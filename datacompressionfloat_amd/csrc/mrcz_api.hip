@@ -815,6 +815,9 @@ extern "C" int mrcz_uncompress_range_async(mrcz_ctx_t *ctx, const void *d_record
 /* ---- digest decode: the CRC-32 of what every chunk decodes to, through the same staging buffer ---- */
 #include "mrcz_digest.hip"
 
+/* ---- probe: the record bytes and the error summary of a compress setting, nothing written ---- */
+#include "mrcz_probe.hip"
+
 /* ---- top-planes decode: the two or three most significant byte planes of every word, the others neither read nor decoded ---- */
 #include "mrcz_top.hip"
 

@@ -22,6 +22,17 @@
  *                                                         the container's header names is refused (255).
  *   -k / -K exclude -e and -r; nothing is written.
  *
+ * Probe, the question before the first container exists (which -b or -e for this volume?):
+ *
+ *   mrc_verify -a vol.mrc -p SPEC                         SPEC = a comma list of bN, bLO:HI (inclusive; b alone = b0:32), eEPS and
+ *                                                         int.  The file streams through the device once, in the runs -a is read
+ *                                                         in; every setting is probed on each resident run (mrcz_probe_chunks:
+ *                                                         nothing is written or decoded).  One line per setting, in the order given:
+ *                                                         "probe <b N | e EPS | int> bytes <container bytes> ratio <file bytes /
+ *                                                         container bytes> max_err <..> rmse <..> psnr_db <..> special_diff <n>".
+ *                                                         Exit status 0; 255 for a bad SPEC or an unreadable file.
+ *   -p excludes -z and everything that goes with a container.
+ *
  * The container is decoded on the device in runs of the context's batch (16 chunks); the original passes through a pinned buffer
  * in the same runs, one mrcz_uncompress_compare per run, one mrcz_compare_finish.  The decoded words are never written anywhere.
  * Prints one "key value" line per field of mrcz_compare_t (include/mrcz_hip.h) and the derived mean_err = sum_err / n_finite,
@@ -56,6 +67,8 @@ static void usage(const char *prog)
     printf("\t-g\tHIP device, default 0\n\n");
     printf("\t-k\tprint the digest sidecar (CRC-32 of the decode) of the container -z, or of the plain file -a when no -z is given\n\n");
     printf("\t-K\tcheck the container -z against this sidecar: exit status 0 all chunks match, 1 some differ\n\n");
+    printf("\t-p\tprobe the plain file -a (no -z): size and error of every setting of the comma list, e.g. b0:12,e0.01,int\n");
+    printf("\t\t(bN, bLO:HI, b = b0:32, eEPS, int), one line each: probe <setting> bytes .. ratio .. max_err .. rmse .. psnr_db .. special_diff ..\n\n");
 }
 
 /* errors leave with the reference's exit(-1) status (255), never through a signal (as mrc_extract) */
@@ -204,13 +217,148 @@ static int digest_main(const char *orig, const char *zip, const char *check, con
     _exit(ok ? 0 : 1);
 }
 
+/* ---- probe: -p ---- */
+
+typedef struct {
+    int xform, bits;
+    float eps;
+    char label[48]; /* "b N", "e EPS" (as given) or "int" */
+} probe_setting_t;
+
+/* the bound as mrc_tar -e takes it: float32 toward zero, finite and > 0 */
+static float probe_eps(const char *s, size_t n)
+{
+    char buf[40], *e = NULL;
+    if (n == 0 || n >= sizeof buf) die("-p: eEPS wants a finite number > 0", NULL);
+    memcpy(buf, s, n);
+    buf[n] = 0;
+    errno = 0;
+    const double v = strtod(buf, &e);
+    if (e == buf || *e || !(v > 0.0) || isinf(v)) die("-p: eEPS wants a finite number > 0", NULL);
+    float f = v > 3.4028234663852886e38 ? 3.4028234663852886e38f : (float)v;
+    if ((double)f > v) { /* rounded up: one step toward zero, so that the bound holds for the value given */
+        uint32_t u;
+        memcpy(&u, &f, 4);
+        u--;
+        memcpy(&f, &u, 4);
+    }
+    if (!(f > 0.0f)) die("-p: eEPS is below the smallest float32", NULL);
+    return f;
+}
+
+/* digits [s, s + n) as a mask level 0..32 */
+static int probe_bits(const char *s, size_t n)
+{
+    if (n == 0 || n > 2) die("-p: bN wants a mask level 0..32", NULL);
+    int v = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (s[i] < '0' || s[i] > '9') die("-p: bN wants a mask level 0..32", NULL);
+        v = 10 * v + (s[i] - '0');
+    }
+    if (v > 32) die("-p: bN wants a mask level 0..32", NULL);
+    return v;
+}
+
+static probe_setting_t *parse_probe_spec(const char *spec, size_t *count)
+{
+    size_t n = 0, cap = 64;
+    probe_setting_t *st = (probe_setting_t *)malloc(cap * sizeof *st);
+    if (!st) die("out of memory", NULL);
+    for (const char *p = spec;;) {
+        const char *q = strchr(p, ',');
+        const size_t len = q ? (size_t)(q - p) : strlen(p);
+        int lo = -1, hi = -1;
+        probe_setting_t one;
+        memset(&one, 0, sizeof one);
+        if (len == 3 && memcmp(p, "int", 3) == 0) {
+            one.xform = MRCZ_PROBE_INT8;
+            strcpy(one.label, "int");
+        } else if (len >= 1 && p[0] == 'e') {
+            one.xform = MRCZ_PROBE_ABS;
+            one.eps = probe_eps(p + 1, len - 1);
+            snprintf(one.label, sizeof one.label, "e %.*s", (int)(len - 1), p + 1);
+        } else if (len >= 1 && p[0] == 'b') {
+            const char *colon = (const char *)memchr(p, ':', len);
+            if (len == 1) { lo = 0; hi = 32; }
+            else if (colon) { lo = probe_bits(p + 1, (size_t)(colon - p - 1)); hi = probe_bits(colon + 1, len - (size_t)(colon - p) - 1); }
+            else lo = hi = probe_bits(p + 1, len - 1);
+            if (lo > hi) die("-p: bLO:HI wants LO <= HI", NULL);
+        } else
+            die("-p: a setting is bN, bLO:HI, b, eEPS or int", NULL);
+        const int reps = lo < 0 ? 1 : hi - lo + 1; /* a range of mask levels is one setting per level */
+        for (int r = 0; r < reps; r++) {
+            if (n == cap) {
+                cap *= 2;
+                st = (probe_setting_t *)realloc(st, cap * sizeof *st);
+                if (!st) die("out of memory", NULL);
+            }
+            if (lo >= 0) {
+                one.xform = MRCZ_PROBE_MASK;
+                one.bits = lo + r;
+                snprintf(one.label, sizeof one.label, "b %d", lo + r);
+            }
+            st[n++] = one;
+        }
+        if (n > 4096) die("-p: too many settings", NULL);
+        if (!q) break;
+        p = q + 1;
+    }
+    *count = n;
+    return st;
+}
+
+static int probe_main(const char *orig, const char *spec, int device)
+{
+    size_t nset = 0;
+    probe_setting_t *st = parse_probe_spec(spec, &nset);
+    const int fd = open(orig, O_RDONLY);
+    struct stat sb;
+    if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) die("cannot open the file", NULL);
+    const uint64_t fsz = (uint64_t)sb.st_size, nfl = fsz / 4, chk = MRCZ_CHUNK_FLOATS, nch = (nfl + chk - 1) / chk;
+    const uint32_t batch = (uint32_t)(nch < BATCH ? (nch ? nch : 1u) : BATCH);
+    mrcz_ctx_t *c = NULL;
+    if (mrcz_create(&c, device, batch) != MRCZ_OK) die("no usable HIP device (the codec has no CPU path)", NULL);
+    const uint64_t run_bytes = 4 * chk * batch, acc_bytes = sizeof(mrcz_compare_t) * (nch ? nch : 1);
+    uint64_t *size = (uint64_t *)calloc(nset, sizeof *size);
+    void *h_in = NULL, *d_in = NULL, *d_acc = NULL; /* d_acc: one run of nch records per setting */
+    if (!size || mrcz_dev_malloc(c, &d_acc, acc_bytes * nset)) die("out of memory", c);
+    if (nch && (mrcz_host_malloc(c, &h_in, run_bytes) || mrcz_dev_malloc(c, &d_in, run_bytes))) die("out of memory", c);
+    for (uint64_t k = 0; k < nch; k += batch) { /* one read and one upload per run of at most `batch` chunks, every setting probed on it */
+        const uint64_t e = k + batch < nch ? k + batch : nch;
+        const uint64_t w0 = k * chk, w1 = e * chk < nfl ? e * chk : nfl;
+        pread_all(fd, h_in, 4 * (w1 - w0), 4 * w0, "read of the file");
+        if (mrcz_copy_h2d(c, d_in, h_in, 4 * (w1 - w0)) != MRCZ_OK) die("copy to the device", c);
+        for (size_t s = 0; s < nset; s++) {
+            uint64_t len = 0;
+            if (mrcz_probe_chunks(c, d_in, w1 - w0, k, st[s].xform, st[s].bits, st[s].eps, -1.0, -1.0,
+                                  (mrcz_compare_t *)((uint8_t *)d_acc + acc_bytes * s), &len, NULL) != MRCZ_OK)
+                die("probe", c);
+            size[s] += len;
+        }
+    }
+    for (size_t s = 0; s < nset; s++) {
+        mrcz_compare_t t;
+        if (mrcz_compare_finish(c, (const mrcz_compare_t *)((uint8_t *)d_acc + acc_bytes * s), 0, nch, &t) != MRCZ_OK) die("compare finish", c);
+        const uint64_t bytes = nfl ? MRCZ_FILE_HEADER_BYTES + size[s] : 0; /* mrc_tar writes nothing for a file of fewer than four bytes */
+        const double rmse = rmse_of(&t);
+        printf("probe %s bytes %" PRIu64 " ratio %.17g max_err %.17g rmse %.17g psnr_db ", st[s].label, bytes, bytes ? (double)fsz / (double)bytes : 0.0,
+               t.max_err, rmse);
+        if (rmse == 0.0) printf("inf");
+        else printf("%.17g", 20.0 * log10((t.orig_max - t.orig_min) / rmse));
+        printf(" special_diff %" PRIu64 "\n", t.n_special_diff);
+    }
+    close(fd);
+    fflush(stdout);
+    _exit(0);
+}
+
 int main(int argc, char *argv[])
 {
-    const char *orig = NULL, *zip = NULL, *dtype = NULL, *check = NULL;
+    const char *orig = NULL, *zip = NULL, *dtype = NULL, *check = NULL, *probe = NULL;
     double eps_abs = -1.0, eps_rel = -1.0;
     int opt, device = 0, per_chunk = 0, print_digest = 0;
     if (argc < 2) { usage(argv[0]); return 255; }
-    while ((opt = getopt(argc, argv, "ha:z:e:r:s:cg:kK:")) != -1) {
+    while ((opt = getopt(argc, argv, "ha:z:e:r:s:cg:kK:p:")) != -1) {
         switch (opt) {
         case 'a': orig = optarg; break;
         case 'z': zip = optarg; break;
@@ -221,9 +369,15 @@ int main(int argc, char *argv[])
         case 'g': device = atoi(optarg); break;
         case 'k': print_digest = 1; break;
         case 'K': check = optarg; break;
+        case 'p': probe = optarg; break;
         case 'h': usage(argv[0]); return 0;
         default: usage(argv[0]); return 255;
         }
+    }
+    if (probe) {
+        if (zip || check || print_digest || dtype || per_chunk || eps_abs >= 0.0 || eps_rel >= 0.0) die("-p probes a plain file: give -a and none of -z, -k, -K, -s, -c, -e, -r", NULL);
+        if (!orig) die("-p wants the file to probe (-a)", NULL);
+        return probe_main(orig, probe, device);
     }
     if (print_digest || check) {
         if (eps_abs >= 0.0 || eps_rel >= 0.0 || per_chunk) die("-k and -K exclude -e, -r and -c", NULL);

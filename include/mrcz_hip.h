@@ -357,6 +357,34 @@ int mrcz_digest_finish(mrcz_ctx_t *ctx, const mrcz_digest_t *d_acc, uint64_t fir
                        mrcz_digest_t *h_total);
 
 /*
+ * Probe: what a compress setting costs and what it buys, before the first container exists.  For words that are on the device and
+ * one setting it gives the exact size of the records and the error summary of what they would decode to, without writing, decoding
+ * or allocating anything of the volume's size: the compressor's sizing passes (everything up to the payload lengths) run, the
+ * layout and emit passes do not, and the error is folded over the original's words and the transform alone.
+ *   mrcz_probe_chunks  d_in (16-byte aligned, only read) = nfloats words that start a chunk boundary of a file, first_chunk as in
+ *                      mrcz_compress_chunks.  xform = MRCZ_PROBE_MASK (bits, 0..32), MRCZ_PROBE_ABS (eps, as
+ *                      mrcz_compress_chunks_abs) or MRCZ_PROBE_INT8.  *out_len and plane_bytes (optional) are exactly what
+ *                      mrcz_compress_chunks / _abs / _int8 return for the same arguments: record bytes, without the 17-byte file
+ *                      header.  d_acc (optional, device, 8-byte aligned, needs no zeroing) receives record first_chunk + i for
+ *                      chunk i of d_in: the mrcz_compare_t that mrcz_uncompress_compare would assign for the container written
+ *                      with that setting, compared against d_in with the bounds eps_abs and eps_rel (negative or NaN: off).
+ *                      Counts, extremes, indices, orig_min and orig_max are equal; the sums follow the same definition and the same
+ *                      order of addition.  The bits of d_acc[c] depend on chunk c's words and the setting only: not on
+ *                      max_batch_chunks, on how a file is cut into calls, or on first_chunk.  mrcz_compare_finish folds the
+ *                      records.  Synchronous; mrcz_probe_chunks_async enqueues on the compute stream, h_result5 as
+ *                      mrcz_compress_chunks_async.  A later compress call on the context is not disturbed.
+ * MRCZ_EINVAL: an unknown xform, bits outside 0..32, an eps that is not finite and > 0, a NULL or misaligned d_in, a misaligned
+ * d_acc, a NULL out_len.  nfloats == 0 is MRCZ_OK with *out_len = 0 and touches nothing.
+ */
+#define MRCZ_PROBE_MASK 0
+#define MRCZ_PROBE_ABS 1
+#define MRCZ_PROBE_INT8 2
+int mrcz_probe_chunks(mrcz_ctx_t *ctx, const void *d_in, uint64_t nfloats, uint64_t first_chunk, int xform, int bits, float eps,
+                      double eps_abs, double eps_rel, mrcz_compare_t *d_acc, uint64_t *out_len, uint64_t plane_bytes[4]);
+int mrcz_probe_chunks_async(mrcz_ctx_t *ctx, const void *d_in, uint64_t nfloats, uint64_t first_chunk, int xform, int bits, float eps,
+                            double eps_abs, double eps_rel, mrcz_compare_t *d_acc, uint64_t *h_result5);
+
+/*
  * Top-planes decode: every word of a run of chunks at reduced precision, the low byte planes neither read nor decoded.  A chunk
  * record is its 16-byte header (the four payload lengths) followed by the payloads of byte planes 0, 1, 2, 3 of the chunk's words;
  * plane 3 is the sign and seven exponent bits of a float32, plane 2 its last exponent bit and top seven mantissa bits.  keep = 2
