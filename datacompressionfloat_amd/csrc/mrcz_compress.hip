@@ -903,14 +903,67 @@ __device__ __forceinline__ void packer_finish(LanePacker &p)
     if (p.nacc > 0) atomicOr(&p.stage[p.word], (uint32_t)p.acc);
 }
 
-constexpr int EMIT_WAVES = 5; /* waves per SIMD: 94 VGPRs, no spills, 6.1 KB of LDS per wave (4: 104 VGPRs, kernel 1.00 ms instead of 0.90; 6: 80 VGPRs, ten of them spilled, 0.93) */
+constexpr int EMIT_WAVES = 5; /* waves per SIMD: 95 VGPRs, no spills, 7.0 KB of LDS per wave (measured with the 288-dword table, 94 VGPRs and 6.1 KB -- 4: 104 VGPRs, kernel 1.00 ms instead of 0.90; 6: 80 VGPRs, ten of them spilled, 0.93) */
 #define OPAQUE4(x, q) asm volatile("" : "+v"((x)[4 * (q)]), "+v"((x)[4 * (q) + 1]), "+v"((x)[4 * (q) + 2]), "+v"((x)[4 * (q) + 3]))
+
+/* k_emit's table of the current block, one dword per symbol a position can start: the symbol's bits (LSB first, ENT_VAL) and
+ * their number above them.
+ *   [0, 256)    the literals
+ *   [256, 512)  the Z_RLE match of length 3 + (i - 256): its length code, above it the value of the extra bits, above that
+ *               the code of distance 1 (symbol 0: one zero bit in a dynamic block, five in a static one) -- at most
+ *               15 + 5 + 5 bits.  A match's distance never varies, so the whole symbol is a function of its length and
+ *               the block's code row: the table is filled when the block changes and replaces len_code, the second
+ *               look-up and the shifts per match. */
+constexpr int EMIT_LUT = 512;
+constexpr int ENT_SH = 26;
+constexpr uint32_t ENT_VAL = (1u << ENT_SH) - 1u;
+
+/* fill lut[] from a block's code row (code | len << 16 per literal/length symbol), all 64 lanes, four lengths each */
+__device__ __forceinline__ void emit_table_fill(uint32_t *lut, const uint32_t *row, uint32_t dbits, int lane)
+{
+    for (int i = lane; i < 256; i += 64) {
+        const uint32_t e = row[i];
+        lut[i] = (e & 0xffffu) | ((e >> 16) << ENT_SH);
+        int xb, xv;
+        const uint32_t m = row[257 + len_code(i + 3, &xb, &xv)];
+        const uint32_t cl = m >> 16;
+        lut[256 + i] = (m & 0xffffu) | ((uint32_t)xv << cl) | ((cl + (uint32_t)xb + dbits) << ENT_SH);
+    }
+}
 
 /* byte j (0..15, run-time) of the four words of a row quarter */
 __device__ __forceinline__ uint32_t quarter_byte(const uint32_t wv[4], int j)
 {
-    const uint64_t lo = (uint64_t)wv[0] | ((uint64_t)wv[1] << 32), hi = (uint64_t)wv[2] | ((uint64_t)wv[3] << 32);
-    return (uint32_t)(((j & 8) ? hi : lo) >> (8 * (j & 7))) & 0xffu;
+    const uint32_t w0 = wv[0], w1 = wv[1], w2 = wv[2], w3 = wv[3]; /* (values: a conditional between array elements selects an address, and the row leaves the registers) */
+    const uint32_t lo = (j & 8) ? w2 : w0, hi = (j & 8) ? w3 : w1;
+    return __builtin_amdgcn_perm(hi, lo, 0x0c0c0c00u | (uint32_t)(j & 7)); /* byte j & 7 of hi:lo, zero-extended */
+}
+
+/* Symbols tile the positions: a match ends where the next symbol starts, so inside a quarter its length is the distance to
+ * the next symbol start of the part (a subtraction).  Only the quarter's last symbol has to look at the lane's run starts,
+ * once per quarter: this is the length it has if it is a match. */
+__device__ __forceinline__ int quarter_last_len(uint32_t Sg, int q, const LaneTile &lt)
+{
+    return match_len_at(lt.E, lt.a, lt.nextS, 16 * q + 31 - __builtin_clz(Sg | 1u));
+}
+
+/* the table entries of the lowest two symbol starts of rem (e1 = 0 if there is one only), which rem loses.  rem != 0.  No
+ * branches: a literal's "length" and a missing second symbol's byte (position 16 reads byte 0) are worked out and not used. */
+struct SymPair { uint32_t e0, e1; };
+__device__ __forceinline__ SymPair quarter_take2(const uint32_t *lut, const uint32_t wv[4], uint32_t &rem, uint32_t Mg, int lastlen)
+{
+    const int j0 = __builtin_ctz(rem);
+    const uint32_t r1 = rem & (rem - 1u);
+    const int j1 = __builtin_ctz(r1 | 0x10000u);
+    const uint32_t r2 = r1 & (r1 - 1u);
+    const int j2 = __builtin_ctz(r2 | 0x10000u);
+    const int len0 = r1 ? j1 - j0 : lastlen, len1 = r2 ? j2 - j1 : lastlen;
+    SymPair p;
+    p.e0 = lut[((Mg >> j0) & 1u) ? (uint32_t)(253 + len0) : quarter_byte(wv, j0)];
+    p.e1 = lut[((Mg >> j1) & 1u) ? (uint32_t)(253 + len1) : quarter_byte(wv, j1)];
+    if (!r1) p.e1 = 0u;
+    rem = r2;
+    return p;
 }
 
 /* pass A of one row quarter (16 positions in the words wv): bits the lane's literals of this quarter produce */
@@ -919,12 +972,12 @@ __device__ __forceinline__ uint32_t quarter_literal_bits(const uint32_t *lut, co
     uint32_t bits = 0;
     if (__ballot(Lg != 0xffffu) == 0ull) { /* everybody has 16 literals: no per-position tests */
 #pragma unroll
-        for (int j = 0; j < 16; j++) bits += lut[(wv[j >> 2] >> (8 * (j & 3))) & 0xffu] >> 16;
+        for (int j = 0; j < 16; j++) bits += lut[(wv[j >> 2] >> (8 * (j & 3))) & 0xffu] >> ENT_SH;
     } else {
 #pragma unroll
         for (int j = 0; j < 16; j++) {
             const uint32_t e = lut[(wv[j >> 2] >> (8 * (j & 3))) & 0xffu];
-            bits += ((Lg >> j) & 1u) ? (e >> 16) : 0u;
+            bits += ((Lg >> j) & 1u) ? (e >> ENT_SH) : 0u;
         }
     }
     return bits;
@@ -932,7 +985,7 @@ __device__ __forceinline__ uint32_t quarter_literal_bits(const uint32_t *lut, co
 
 /* pass B of one row quarter: append the codes of the symbols that start in it */
 __device__ __forceinline__ void quarter_emit(LanePacker &pk, const uint32_t *lut, const uint32_t wv[4], uint32_t Sg, uint32_t Mg,
-                                             int q, const LaneTile &lt, uint32_t dbits)
+                                             int q, const LaneTile &lt)
 {
     if (__ballot(Mg != 0u || Sg != 0xffffu) == 0ull) {
         /* literals only, for every lane (the interior of a coded plane): two codes (<= 15 bits each) are joined in 32 bits
@@ -941,34 +994,24 @@ __device__ __forceinline__ void quarter_emit(LanePacker &pk, const uint32_t *lut
         for (int j = 0; j < 16; j += 2) {
             const uint32_t e0 = lut[(wv[j >> 2] >> (8 * (j & 3))) & 0xffu];
             const uint32_t e1 = lut[(wv[(j + 1) >> 2] >> (8 * ((j + 1) & 3))) & 0xffu];
-            const uint32_t n0 = e0 >> 16;
-            packer_put(pk, (e0 & 0xffffu) | ((e1 & 0xffffu) << n0), (int)(n0 + (e1 >> 16)));
+            const uint32_t n0 = e0 >> ENT_SH;
+            packer_put(pk, (e0 & ENT_VAL) | ((e1 & ENT_VAL) << n0), (int)(n0 + (e1 >> ENT_SH)));
         }
         return;
     }
     /* runs and literals mixed (exponent planes, masked planes): walk the lane's symbols, not its positions -- a match covers
-     * at least three positions, so there are far fewer of them, and the match arithmetic runs once per match instead of once
-     * per position in which any lane of the wave happens to have one */
+     * at least three positions, so there are far fewer of them -- and two symbols per trip, as on the literal path: both
+     * entries are read together and joined, v0 | v1 << n0.  A pair has up to 25 + 25 bits: the low 32 are appended, then,
+     * rarely, the high half.  A lane with an odd count appends its last symbol alone (e1 = 0). */
+    const int lastlen = quarter_last_len(Sg, q, lt);
     uint32_t rem = Sg;
     while (__ballot(rem != 0u)) {
         if (rem) {
-            const int j = __builtin_ctz(rem);
-            rem &= rem - 1u;
-            uint32_t val;
-            int nb;
-            if ((Mg >> j) & 1u) {
-                int xb, xv;
-                const int code = len_code(match_len_at(lt.E, lt.a, lt.nextS, 16 * q + j), &xb, &xv);
-                const uint32_t e = lut[257 + code];
-                const int cl = (int)(e >> 16);
-                val = (e & 0xffffu) | ((uint32_t)xv << cl);
-                nb = cl + xb + (int)dbits;
-            } else {
-                const uint32_t e = lut[quarter_byte(wv, j)];
-                val = e & 0xffffu;
-                nb = (int)(e >> 16);
-            }
-            packer_put(pk, val, nb);
+            const SymPair p = quarter_take2(lut, wv, rem, Mg, lastlen);
+            const uint32_t n0 = p.e0 >> ENT_SH, v1 = p.e1 & ENT_VAL;
+            const int nb = (int)(n0 + (p.e1 >> ENT_SH));
+            packer_put(pk, (p.e0 & ENT_VAL) | (v1 << n0), nb < 32 ? nb : 32);
+            if (nb > 32) packer_put(pk, v1 >> (32u - n0), nb - 32); /* (n0 >= 8 here) */
         }
     }
 }
@@ -983,7 +1026,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))
      * registers for both passes: an LDS copy of the tile costs 5 KB per wave and with it a third of the occupancy, and this
      * kernel waits on LDS look-ups, so it is as fast as the number of waves that hide them. */
     __shared__ __attribute__((aligned(16))) uint32_t stage[STAGE_WORDS];
-    __shared__ uint32_t lut[HROW];
+    __shared__ uint32_t lut[EMIT_LUT];
     const uint32_t g = blockIdx.x, c = blockIdx.y;
     const uint64_t cbase = (uint64_t)c * CHK;
     const uint32_t n = (uint32_t)((nfloats - cbase) < CHK ? (nfloats - cbase) : CHK);
@@ -1001,7 +1044,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))
     uint32_t cur = 0;        /* stream bit offset where the next symbol of the current block goes */
     int mode = -1;           /* 0 stored, 1 static, 2 dynamic */
     uint32_t blkEnd = 0;     /* position where the current block ends */
-    uint32_t dbits = 0;      /* distance-code bits per match (1 dynamic, 5 static) */
     /* The bits a wave writes into one coded block are one bit string (its pair), produced a tile part at a time.  The
      * dword in which one part ends and the next begins is carried from part to part and stored once it is full; only
      * the pair's first word (when the pair starts inside it) and its last, unfinished word meet another writer and
@@ -1058,19 +1100,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))
                 blkEnd = bstart[curBlk + 1];
                 if (mode == 0) cur = L.databit + 8u * (t0 + (uint32_t)pos0 - bstart[curBlk]);
                 else {
+                    /* the block's table: its code row goes through the staging buffer, which is idle between parts */
                     __builtin_amdgcn_wave_barrier(); /* the previous block's table readers are done */
                     if (mode == 2) {
                         const uint32_t *code = blkcode + ((size_t)s * MAXBLK + curBlk) * HROW;
-                        for (int i = lane; i < 286; i += 64) lut[i] = code[i];
-                        dbits = 1;
+                        for (int i = lane; i < 286; i += 64) stage[i] = code[i];
                     } else {
                         for (int i = lane; i < 286; i += 64) {
                             int l;
                             const uint32_t cd = static_lcode(i, &l);
-                            lut[i] = cd | ((uint32_t)l << 16);
+                            stage[i] = cd | ((uint32_t)l << 16);
                         }
-                        dbits = 5;
                     }
+                    __builtin_amdgcn_wave_barrier();
+                    emit_table_fill(lut, stage, mode == 2 ? 1u : 5u /* bits of distance code 0 */, lane);
                     cur = pairoff[(size_t)s * MAXPAIR + (g + curBlk)];
                     __builtin_amdgcn_wave_barrier(); /* lut visible to the whole wave */
                 }
@@ -1118,7 +1161,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))
             const uint64_t S = cls.S & pm, M = cls.M & pm;
 
             /* pass A: bits produced by this lane.  The table reads of a quarter are independent (unrolled, bytes come from
-             * registers), so their LDS latency overlaps; matches are rare and handled apart. */
+             * registers), so their LDS latency overlaps; matches are handled apart, over the whole row (in the chunks of a long
+             * run that is one trip per tile; walking the symbols two at a time as pass B does was measured: slower). */
             if (__ballot(S != 0ull) == 0ull) { pos0 = pos1; cap = len; continue; } /* no symbol starts in this part (inside long runs) */
             uint32_t lbits = 0;
             {
@@ -1131,11 +1175,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))
                     lbits += quarter_literal_bits(lut, &x[4 * q], Lg);
                 }
                 uint64_t m = M;
-                while (m) {
+                while (m) { /* a match's bits: one table read by its length */
                     const int i = ctz64(m); m &= m - 1;
-                    int xb, xv;
-                    const int code = len_code(match_len_at(lt.E, lt.a, lt.nextS, i), &xb, &xv);
-                    lbits += (lut[257 + code] >> 16) + (uint32_t)xb + dbits;
+                    lbits += lut[253 + match_len_at(lt.E, lt.a, lt.nextS, i)] >> ENT_SH;
                 }
             }
             uint32_t tot;
@@ -1163,7 +1205,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))
                     const uint32_t Sg = (uint32_t)(S >> (16 * q)) & 0xffffu, Mg = (uint32_t)(M >> (16 * q)) & 0xffffu;
                     if (__ballot(Sg != 0u) == 0ull) continue; /* wave-uniform: no symbol starts in this quarter */
                     OPAQUE4(x, q);
-                    quarter_emit(pk, lut, &x[4 * q], Sg, Mg, q, lt, dbits);
+                    quarter_emit(pk, lut, &x[4 * q], Sg, Mg, q, lt);
                 }
                 packer_finish(pk);
                 __builtin_amdgcn_wave_barrier();
