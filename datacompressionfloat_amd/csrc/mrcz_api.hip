@@ -66,9 +66,8 @@ struct mrcz_ctx {
     uint32_t *blkhdr;
     BlkMeta *meta;
     BlkLay *lay;
-    uint32_t *pairbits;
+    uint2 *pairbits;       /* bits of every pair under its block's dynamic (.x) and the static (.y) code */
     uint32_t *pairoff;
-    uint32_t *blkbase;
     uint64_t *result;      /* device: [0] running byte offset, [1..4] plane sums / error */
     uint64_t *h_result;    /* pinned host mirror */
     DecStream *dstreams;
@@ -197,7 +196,6 @@ extern "C" int mrcz_create(mrcz_ctx_t **out, int device, uint32_t max_batch_chun
     if (e == hipSuccess) e = dalloc(&ctx->lay, ns * MAXBLK);
     if (e == hipSuccess) e = dalloc(&ctx->pairbits, ns * MAXPAIR);
     if (e == hipSuccess) e = dalloc(&ctx->pairoff, ns * MAXPAIR);
-    if (e == hipSuccess) e = dalloc(&ctx->blkbase, ns + MAX_LANES); /* one prefix array per lane */
     if (e == hipSuccess) e = dalloc(&ctx->result, 16);
     if (e == hipSuccess) e = dalloc(&ctx->dstreams, ns);
     if (e == hipSuccess) e = dalloc(&ctx->fallback, ns);
@@ -238,7 +236,7 @@ extern "C" void mrcz_destroy(mrcz_ctx_t *ctx)
     (void)hipFree(ctx->tsum); (void)hipFree(ctx->tinfo); (void)hipFree(ctx->sinfo); (void)hipFree(ctx->blkstart);
     (void)hipFree(ctx->slideq); (void)hipFree(ctx->pairhist); (void)hipFree(ctx->blkfreq); (void)hipFree(ctx->blkcode);
     (void)hipFree(ctx->blkhdr); (void)hipFree(ctx->meta); (void)hipFree(ctx->lay); (void)hipFree(ctx->pairbits);
-    (void)hipFree(ctx->pairoff); (void)hipFree(ctx->blkbase); (void)hipFree(ctx->result); (void)hipFree(ctx->dstreams); (void)hipFree(ctx->fallback); (void)hipFree(ctx->cands); (void)hipFree(ctx->ncand); (void)hipFree(ctx->candbase); (void)hipFree(ctx->jobord); (void)hipFree(ctx->segs); (void)hipFree(ctx->nseg); (void)hipFree(ctx->segidx); (void)hipFree(ctx->rawlist); (void)hipFree(ctx->scratch); (void)hipFree(ctx->hdrs); (void)hipFree(ctx->njobs);
+    (void)hipFree(ctx->pairoff); (void)hipFree(ctx->result); (void)hipFree(ctx->dstreams); (void)hipFree(ctx->fallback); (void)hipFree(ctx->cands); (void)hipFree(ctx->ncand); (void)hipFree(ctx->candbase); (void)hipFree(ctx->jobord); (void)hipFree(ctx->segs); (void)hipFree(ctx->nseg); (void)hipFree(ctx->segidx); (void)hipFree(ctx->rawlist); (void)hipFree(ctx->scratch); (void)hipFree(ctx->hdrs); (void)hipFree(ctx->njobs);
     (void)hipFree(ctx->dbgphase);
     (void)hipFree(ctx->planes);
     (void)hipFree(ctx->stage);
@@ -371,9 +369,8 @@ static int compress_lane(mrcz_ctx *ctx, hipStream_t lstream, int phase, int slot
     uint32_t *blkhdr = ctx->blkhdr + (size_t)s0 * MAXBLK * HDRWORDS;
     BlkMeta *meta = ctx->meta + (size_t)s0 * MAXBLK;
     BlkLay *lay = ctx->lay + (size_t)s0 * MAXBLK;
-    uint32_t *pairbits = ctx->pairbits + (size_t)s0 * MAXPAIR;
+    uint2 *pairbits = ctx->pairbits + (size_t)s0 * MAXPAIR;
     uint32_t *pairoff = ctx->pairoff + (size_t)s0 * MAXPAIR;
-    uint32_t *blkbase = ctx->blkbase + s0 + (uint32_t)slot; /* lane l needs 4 nb_l + 1 entries */
     uint8_t *planes = ctx->planes + (size_t)s0 * CHK;
     if (phase == 0) {
         if (xf == Xform::Quant) LAUNCH("k_tile_summary", k_tile_summary<Xform::Quant>, dim3(SPS, nb), dim3(256), bin, bfl, mask, fstart, tsum, planes);
@@ -383,17 +380,15 @@ static int compress_lane(mrcz_ctx *ctx, hipStream_t lstream, int phase, int slot
         /* waves per workgroup by batch size: 4 up to 12 chunks, else 1 */
         if (nb <= 12u) LAUNCH("k_histogram", k_histogram<4>, dim3(SPS, nb, 4), dim3(256), planes, bfl, tinfo, pairhist, blkstart, slideq, HIST_FEW);
         else LAUNCH("k_histogram", k_histogram<1>, dim3(SPS, nb, 4), dim3(64), planes, bfl, tinfo, pairhist, blkstart, slideq, HIST_FEW);
-        LAUNCH("k_block_reduce", k_block_reduce, dim3(MAXBLK, ns), dim3(64), tinfo, sinfo, pairhist, blkfreq);
-        LAUNCH("k_block_index", k_block_index, dim3(1), dim3(256), sinfo, ns, blkbase);
+        LAUNCH("k_block_reduce", k_block_reduce, dim3(MAXBLK, ns), dim3(64 * BR_WAVES), tinfo, sinfo, pairhist, blkfreq);
         HIPCHK(hipEventRecord(ctx->ev_stream[slot], lstream), "event"); /* this lane's streaming passes are done: the next lane may start */
         unsigned long long *hdbg = ctx->phase_profile == 3 ? ctx->dbgphase : (unsigned long long *)NULL; /* developer tool */
-        /* trees one thread each, then the header of every block one wave each (the grid covers the most blocks a batch can
-         * have; the kernel reads the count from blkbase) */
-        LAUNCH("k_huffman", k_huffman, dim3((ns * MAXBLK + HUFF_TREES - 1) / HUFF_TREES), dim3(HUFF_TREES), sinfo, ns, blkbase, blkfreq, blkcode, blkhdr, meta, hdbg);
-        LAUNCH("k_huffman_hdr", k_huffman_hdr, dim3(ns * MAXBLK), dim3(64), sinfo, ns, blkbase, blkcode, blkhdr, meta);
-        LAUNCH("k_stream_layout", k_stream_layout, dim3(ns), dim3(64), sinfo, meta, blkstart, slideq, lay);
-        LAUNCH("k_pair_bits", k_pair_bits, dim3(SPS, ns), dim3(64), sinfo, lay, pairhist, blkcode, tinfo, pairbits);
-        LAUNCH("k_pair_offsets", k_pair_offsets, dim3(ns), dim3(64), sinfo, lay, tinfo, pairbits, pairoff);
+        /* trees one thread each, packed over the lane's streams (the grid covers the most blocks a lane can have; every
+         * workgroup counts the real ones itself); then one wave for the header of every block and one for the pair bits
+         * of every segment, in one grid; then block and pair offsets, one wave a stream */
+        LAUNCH("k_huffman", k_huffman, dim3((ns * MAXBLK + HUFF_TREES - 1) / HUFF_TREES), dim3(HUFF_TREES), sinfo, ns, blkfreq, blkcode, blkhdr, meta, hdbg);
+        LAUNCH("k_huffman_hdr", k_huffman_hdr, dim3(MAXBLK + SPS, ns), dim3(64), sinfo, blkcode, blkhdr, meta, pairhist, tinfo, pairbits);
+        LAUNCH("k_stream_layout", k_stream_layout, dim3(ns), dim3(64), sinfo, meta, blkstart, slideq, lay, tinfo, pairbits, pairoff);
     } else if (phase == 1) {
         LAUNCH("k_container", k_container, dim3(1), dim3(256), sinfo, nb, out, ctx->result);
     } else {
@@ -475,7 +470,7 @@ static int compress_enqueue(mrcz_ctx_t *ctx, const void *d_in, uint64_t nfloats,
                 }
                 if (phase == 2 && l + 1u < nlanes) {
                     /* The emit kernel fills every CU for as long as it runs, and small kernels queued behind it on another
-                     * stream wait for hundreds of microseconds (measured: k_block_index, one workgroup, 333 us).  The next
+                     * stream wait for hundreds of microseconds (measured: a kernel of one workgroup, 333 us).  The next
                      * lane's Huffman kernel is what the end of the batch hangs on, so this lane's emit does not start before
                      * that lane's streaming passes are through and its Huffman kernel is next in line. */
                     HIPCHK(hipStreamWaitEvent(st, ctx->ev_stream[l + 1u], 0), "wait");

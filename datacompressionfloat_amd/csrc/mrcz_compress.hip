@@ -16,8 +16,7 @@
  *                                window-slide positions (App. B.4)
  *   k_block_reduce   small     : block histograms
  *   k_huffman        small     : zlib-exact Huffman construction, dynamic headers      (mrcz_huffman.hip)
- *   k_stream_layout  small     : stored/static/dynamic choice, block bit offsets, RAW test
- *   k_pair_bits/_off small     : bit offset of every pair
+ *   k_stream_layout  small     : stored/static/dynamic choice, block bit offsets, RAW test, bit offset of every pair
  *   k_container      small     : payload offsets + 16-byte chunk headers
  *   k_clear_boundaries small   : zero the few words in which two writers meet (the output is not zero-filled)
  *   k_emit           N B x 4 read, Z B written : Huffman/stored/raw bit packing, whole words
@@ -497,39 +496,42 @@ __global__ __launch_bounds__(64 * W) void k_histogram(const uint8_t *__restrict_
 /* ======================================================================================
  * block histograms = sum of the block's pairs
  * ==================================================================================== */
-constexpr int BR_ROWS = 8;  /* pair rows k_block_reduce has in flight */
-__global__ __launch_bounds__(64) void k_block_reduce(const TileInfo *__restrict__ tinfo, const StreamInfo *__restrict__ sinfo,
-                                                     const uint16_t *__restrict__ pairhist, uint16_t *__restrict__ blkfreq)
+constexpr int BR_ROWS = 8;  /* pair rows a wave of k_block_reduce has in flight */
+constexpr int BR_WAVES = 4; /* waves that share the rows of one block */
+constexpr int BR_LANES = 5 * 64; /* a row as the lanes hold it: 5 values a lane (HROW = 288 of them are real) */
+__global__ __launch_bounds__(64 * BR_WAVES) void k_block_reduce(const TileInfo *__restrict__ tinfo, const StreamInfo *__restrict__ sinfo,
+                                                                const uint16_t *__restrict__ pairhist, uint16_t *__restrict__ blkfreq)
 {
+    __shared__ uint32_t s_P[SPS + 1];
+    __shared__ uint32_t s_part[(BR_WAVES - 1) * BR_LANES];
     const uint32_t b = blockIdx.x, s = blockIdx.y;
     const StreamInfo si = sinfo[s];
     if (b >= si.nblk) return;
-    const int lane = lane_id();
+    const int lane = lane_id(), wave = (int)threadIdx.x >> 6;
     /* segments g with  Pseg[g] < 32767 (b+1)  and  Pseg[g+1] >= 32767 b   (Pseg[nseg] = nsym) */
     const uint32_t lo = b * BLK_SYMS, hi = (b + 1u) * BLK_SYMS;
     const TileInfo *ti = tinfo + (size_t)s * TPS;
-    /* gLast = max g with Pseg[g] < hi ; gFirst = min g with Pseg[g+1] >= lo */
-    int gl = 0, gf = 0;
-    {
-        int a = 0, z = (int)si.nseg - 1; /* Pseg monotone non-decreasing */
-        while (a < z) {
-            const int m = (a + z + 1) >> 1;
-            if (ti[m * TILES_PER_SEG].P < hi) a = m; else z = m - 1;
-        }
-        gl = a;
-        a = 0;
-        z = (int)si.nseg - 1;
-        while (a < z) {
-            const int m = (a + z) >> 1;
-            const uint32_t pn = (m + 1 < (int)si.nseg) ? ti[(m + 1) * TILES_PER_SEG].P : si.nsym;
-            if (pn >= lo) z = m; else a = m + 1;
-        }
-        gf = a;
+    /* gLast = max g with Pseg[g] < hi ; gFirst = min g with Pseg[g+1] >= lo.  Pseg is monotone non-decreasing, so both are
+     * counts: every thread loads one of the <= 192 prefixes (one memory round trip instead of the sixteen dependent ones of
+     * two binary searches), and each wave counts them with ballots. */
+    if (threadIdx.x <= si.nseg && threadIdx.x <= (uint32_t)SPS)
+        s_P[threadIdx.x] = threadIdx.x < si.nseg ? ti[threadIdx.x * TILES_PER_SEG].P : si.nsym;
+    __syncthreads();
+    int gl = -1, gf = 0;
+#pragma unroll
+    for (int k = 0; k < (SPS + 63) / 64; k++) {
+        const uint32_t g = (uint32_t)(lane + 64 * k);
+        const bool in = g < si.nseg;
+        gl += popc64(__ballot(in && s_P[g] < hi));
+        gf += popc64(__ballot(in && s_P[g + 1u] < lo));
     }
-    /* A block of an all-zero plane is the whole chunk: 192 pairs, summed by this one wave -- and the kernel lasts as long as
-     * its longest wave (measured 84 us for 3 chunks, 110 for 43, one row per memory round trip).  Eight rows per round trip. */
+    if (gl < 0) gl = 0;
+    if (gf > (int)si.nseg - 1) gf = (int)si.nseg - 1;
+    /* A block of an all-zero plane is the whole chunk: 192 pairs.  One wave summed them eight rows per memory round trip, 24
+     * dependent trips, and the kernel lasted as long as that wave; the block's rows now go round the BR_WAVES waves in groups
+     * of eight, and the partial rows meet in LDS.  (Sums of integers: the order does not show.) */
     uint32_t acc[5] = {0, 0, 0, 0, 0};
-    for (int g0 = gf; g0 <= gl; g0 += BR_ROWS) {
+    for (int g0 = gf + wave * BR_ROWS; g0 <= gl; g0 += BR_WAVES * BR_ROWS) {
         uint32_t v[BR_ROWS][5];
 #pragma unroll
         for (int j = 0; j < BR_ROWS; j++) {
@@ -546,6 +548,15 @@ __global__ __launch_bounds__(64) void k_block_reduce(const TileInfo *__restrict_
 #pragma unroll
             for (int k = 0; k < 5; k++) acc[k] += v[j][k];
     }
+    if (gl - gf >= BR_ROWS) { /* (the same for every wave of the workgroup) */
+        if (wave)
+            for (int k = 0; k < 5; k++) s_part[(wave - 1) * BR_LANES + lane + 64 * k] = acc[k];
+        __syncthreads();
+        if (wave == 0)
+            for (int w = 0; w < BR_WAVES - 1; w++)
+                for (int k = 0; k < 5; k++) acc[k] += s_part[w * BR_LANES + lane + 64 * k];
+    }
+    if (wave) return;
     uint16_t *dst = blkfreq + ((size_t)s * MAXBLK + b) * HROW;
     for (int k = 0; k < 5; k++) {
         const int i = lane + 64 * k;
@@ -573,9 +584,15 @@ __device__ __forceinline__ uint32_t bitmap_apply(const BitMap f, uint32_t x) { r
 
 __global__ __launch_bounds__(64) void k_stream_layout(StreamInfo *__restrict__ sinfo, const BlkMeta *__restrict__ meta,
                                                       const uint32_t *__restrict__ blkstart,
-                                                      const uint32_t *__restrict__ slideq, BlkLay *__restrict__ lay)
+                                                      const uint32_t *__restrict__ slideq, BlkLay *__restrict__ lay,
+                                                      const TileInfo *__restrict__ tinfo, const uint2 *__restrict__ pairbits,
+                                                      uint32_t *__restrict__ pairoff)
 {
     __shared__ uint32_t s_q[MAXSLIDE];
+    __shared__ uint32_t s_databit[MAXBLK];
+    __shared__ uint8_t s_btype[MAXBLK];
+    __shared__ uint32_t s_val[MAXPAIR];
+    __shared__ uint8_t s_head[MAXPAIR];
     const uint32_t s = blockIdx.x;
     StreamInfo si = sinfo[s];
     const int lane = lane_id();
@@ -640,9 +657,10 @@ __global__ __launch_bounds__(64) void k_stream_layout(StreamInfo *__restrict__ s
         }
         L.endbit = bit;
         lay[(size_t)s * MAXBLK + b0 + (uint32_t)r] = L;
+        s_databit[b0 + (uint32_t)r] = L.databit;
+        s_btype[b0 + (uint32_t)r] = (uint8_t)L.btype;
     }
     const uint32_t total = (uint32_t)__shfl((int)bitmap_apply(inc, 0u), 63);
-    if (lane != 0) return;
     si.zbits = total;
     const uint32_t zlen = ((total + 3u + 7u) >> 3) + 4u; /* 000, pad, 00 00 FF FF */
     si.zlen = zlen;
@@ -650,61 +668,16 @@ __global__ __launch_bounds__(64) void k_stream_layout(StreamInfo *__restrict__ s
     const uint32_t len = zlen > CHK ? CHK : zlen;
     si.raw = (si.n > len + 4u) ? 0u : 1u;
     si.paylen = si.raw ? si.n : zlen;
-    sinfo[s] = si;
-}
+    if (lane == 0) sinfo[s] = si;
+    __builtin_amdgcn_wave_barrier();
 
-/* ======================================================================================
- * pair bit counts and offsets
- * ==================================================================================== */
-__global__ __launch_bounds__(64) void k_pair_bits(const StreamInfo *__restrict__ sinfo, const BlkLay *__restrict__ lay,
-                                                  const uint16_t *__restrict__ pairhist, const uint32_t *__restrict__ blkcode,
-                                                  const TileInfo *__restrict__ tinfo, uint32_t *__restrict__ pairbits)
-{
-    /* one wave per (segment, stream); handles the <= 3 blocks the segment touches */
-    const uint32_t g = blockIdx.x, s = blockIdx.y;
-    const StreamInfo si = sinfo[s];
-    if (g >= si.nseg) return;
-    const int lane = lane_id();
-    const TileInfo *ti = tinfo + (size_t)s * TPS;
-    const uint32_t p0 = ti[g * TILES_PER_SEG].P;
-    const uint32_t p1 = (g + 1 < si.nseg) ? ti[(g + 1) * TILES_PER_SEG].P : si.nsym;
-    const uint32_t b0 = p0 / BLK_SYMS, b1 = p1 / BLK_SYMS;
-    for (uint32_t b = b0; b <= b1; b++) {
-        uint32_t bits = 0;
-        if (b < si.nblk && si.raw == 0) {
-            const uint32_t bt = lay[(size_t)s * MAXBLK + b].btype;
-            if (bt != 0) {
-                const uint16_t *h = pairhist + ((size_t)s * MAXPAIR + (g + b)) * HROW;
-                const uint32_t *code = blkcode + ((size_t)s * MAXBLK + b) * HROW;
-                for (int k = 0; k < 5; k++) {
-                    const int i = lane + 64 * k;
-                    if (i < 286) {
-                        const uint32_t f = h[i];
-                        uint32_t l = (bt == 2) ? (code[i] >> 16) : (uint32_t)static_llen(i);
-                        if (i >= 257) l += (uint32_t)len_extra_bits(i - 257) + (bt == 2 ? 1u : 5u); /* + distance code */
-                        bits += f * l;
-                    }
-                }
-            }
-        }
-        bits = wave_sum_u(bits);
-        if (lane == 0) pairbits[(size_t)s * MAXPAIR + (g + b)] = bits;
-    }
-}
-
-__global__ __launch_bounds__(64) void k_pair_offsets(const StreamInfo *__restrict__ sinfo, const BlkLay *__restrict__ lay,
-                                                     const TileInfo *__restrict__ tinfo, const uint32_t *__restrict__ pairbits,
-                                                     uint32_t *__restrict__ pairoff)
-{
-    /* Pair (g, b) = the part of block b that lies in segment g, pair id g + b; the pairs of a stream in id order walk
+    /* ---- where every pair's bits start ----
+     * Pair (g, b) = the part of block b that lies in segment g, pair id g + b; the pairs of a stream in id order walk
      * through the segments and, inside a segment, through the blocks it touches.  Where a pair's bits start: at the
      * block's data bit if it is the block's first pair, else behind the pair before it.  That is a segmented prefix sum
-     * over the pair ids: val[i] = data bit of the block (head) or the bits of pair i - 1. */
-    __shared__ uint32_t s_val[MAXPAIR];
-    __shared__ uint8_t s_head[MAXPAIR];
-    const uint32_t s = blockIdx.x;
-    const StreamInfo si = sinfo[s];
-    const int lane = lane_id();
+     * over the pair ids: val[i] = data bit of the block (head) or the bits of pair i - 1.  A pair's bits were counted
+     * under both codes its block could get (pair_bits_segment, beside the headers); the block's type, known since a few
+     * lines ago, picks one.  A stored block's pairs, and those of a RAW plane, count 0. */
     const TileInfo *ti = tinfo + (size_t)s * TPS;
     const uint32_t npair = si.nseg ? si.nseg + si.nsym / BLK_SYMS : 0u; /* the last segment ends in block nsym / BLK_SYMS */
     for (uint32_t g = lane; g < si.nseg; g += 64) {
@@ -715,19 +688,27 @@ __global__ __launch_bounds__(64) void k_pair_offsets(const StreamInfo *__restric
             if (i >= (uint32_t)MAXPAIR) break;
             const bool head = b > bs || g == 0u; /* the block's first pair */
             s_head[i] = head ? 1 : 0;
-            s_val[i] = head ? (b < si.nblk ? lay[(size_t)s * MAXBLK + b].databit : 0u) : pairbits[(size_t)s * MAXPAIR + i - 1u];
+            uint32_t v = 0;
+            if (b < si.nblk) {
+                if (head) v = s_databit[b];
+                else if (si.raw == 0u && s_btype[b] != 0u) { /* pair i - 1 is the part of the same block in the segment before */
+                    const uint2 pb = pairbits[(size_t)s * MAXPAIR + i - 1u];
+                    v = s_btype[b] == 2u ? pb.x : pb.y;
+                }
+            }
+            s_val[i] = v;
         }
     }
     __builtin_amdgcn_wave_barrier();
-    constexpr int R = (MAXPAIR + 63) / 64;
-    const uint32_t per = (npair + 63u) / 64u;
-    const uint32_t i0 = (uint32_t)lane * per;
+    constexpr int RP = (MAXPAIR + 63) / 64;
+    const uint32_t perp = (npair + 63u) / 64u;
+    const uint32_t i0 = (uint32_t)lane * perp;
     /* lane-local segmented sums, then a wave scan of (has a head, sum since the last head) */
     uint32_t sum = 0, flag = 0;
 #pragma unroll
-    for (int r = 0; r < R; r++) {
+    for (int r = 0; r < RP; r++) {
         const uint32_t i = i0 + (uint32_t)r;
-        if ((uint32_t)r >= per || i >= npair) continue;
+        if ((uint32_t)r >= perp || i >= npair) continue;
         if (s_head[i]) { sum = s_val[i]; flag = 1; } else sum += s_val[i];
     }
     uint32_t isum = sum, iflag = flag;
@@ -739,11 +720,50 @@ __global__ __launch_bounds__(64) void k_pair_offsets(const StreamInfo *__restric
     if (lane == 0) run = 0;
     uint32_t *po = pairoff + (size_t)s * MAXPAIR;
 #pragma unroll
-    for (int r = 0; r < R; r++) {
+    for (int r = 0; r < RP; r++) {
         const uint32_t i = i0 + (uint32_t)r;
-        if ((uint32_t)r >= per || i >= npair) continue;
+        if ((uint32_t)r >= perp || i >= npair) continue;
         run = s_head[i] ? s_val[i] : run + s_val[i];
         po[i] = run;
+    }
+}
+
+/* ======================================================================================
+ * pair bit counts
+ * ==================================================================================== */
+/* The bits of the <= 3 pairs of segment g, one wave.  They need the pair rows and the code rows only, not the blocks' types
+ * (which hang on the dynamic headers' sizes), so they are counted under both codes a coded block can get -- .x its own
+ * dynamic code, .y the static one -- in the workgroups k_huffman_hdr's grid has besides the headers', off the path from
+ * the trees to the layout.  k_stream_layout picks. */
+__device__ __forceinline__ void pair_bits_segment(uint32_t g, uint32_t s, const StreamInfo *__restrict__ sinfo,
+                                                  const uint16_t *__restrict__ pairhist, const uint32_t *__restrict__ blkcode,
+                                                  const TileInfo *__restrict__ tinfo, uint2 *__restrict__ pairbits)
+{
+    const StreamInfo si = sinfo[s];
+    if (g >= si.nseg) return;
+    const int lane = lane_id();
+    const TileInfo *ti = tinfo + (size_t)s * TPS;
+    const uint32_t p0 = ti[g * TILES_PER_SEG].P;
+    const uint32_t p1 = (g + 1 < si.nseg) ? ti[(g + 1) * TILES_PER_SEG].P : si.nsym;
+    const uint32_t b0 = p0 / BLK_SYMS, b1 = p1 / BLK_SYMS;
+    for (uint32_t b = b0; b <= b1; b++) {
+        uint32_t dyn = 0, sta = 0;
+        if (b < si.nblk) {
+            const uint16_t *h = pairhist + ((size_t)s * MAXPAIR + (g + b)) * HROW;
+            const uint32_t *code = blkcode + ((size_t)s * MAXBLK + b) * HROW;
+            for (int k = 0; k < 5; k++) {
+                const int i = lane + 64 * k;
+                if (i < 286) {
+                    const uint32_t f = h[i];
+                    const uint32_t xb = i >= 257 ? (uint32_t)len_extra_bits(i - 257) : 0u;
+                    dyn += f * ((code[i] >> 16) + xb + (i >= 257 ? 1u : 0u)); /* + the distance code: 1 bit, or 5 */
+                    sta += f * ((uint32_t)static_llen(i) + xb + (i >= 257 ? 5u : 0u));
+                }
+            }
+        }
+        dyn = wave_sum_u(dyn);
+        sta = wave_sum_u(sta);
+        if (lane == 0) pairbits[(size_t)s * MAXPAIR + (g + b)] = make_uint2(dyn, sta);
     }
 }
 

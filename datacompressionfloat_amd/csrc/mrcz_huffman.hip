@@ -306,46 +306,20 @@ template <int HT> __device__ __forceinline__ int bl_tree_build(TreeMem<HT> &tm, 
     return max_blindex;
 }
 
-/* blkbase[s] = number of blocks in streams < s (exclusive prefix), blkbase[nstreams] = total */
-__global__ __launch_bounds__(256) void k_block_index(const StreamInfo *__restrict__ sinfo, uint32_t nstreams,
-                                                     uint32_t *__restrict__ blkbase)
-{
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (uint32_t s0 = 0; s0 < nstreams; s0 += 256) {
-        const uint32_t s = s0 + threadIdx.x;
-        const uint32_t v = s < nstreams ? sinfo[s].nblk : 0u;
-        /* simple Hillis-Steele over the 4 waves via shared memory */
-        __shared__ uint32_t buf[256];
-        buf[threadIdx.x] = v;
-        __syncthreads();
-        for (int d = 1; d < 256; d <<= 1) {
-            const uint32_t y = threadIdx.x >= (unsigned)d ? buf[threadIdx.x - d] : 0u;
-            __syncthreads();
-            buf[threadIdx.x] += y;
-            __syncthreads();
-        }
-        if (s < nstreams) blkbase[s] = carry + buf[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 255) carry += buf[255];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) blkbase[nstreams] = carry;
-}
-
 /* Trees (threads) per workgroup: 1.5 KB of LDS per tree.  48 (74 KB, two workgroups per CU) packs a wave best. */
 constexpr int HUFF_TREES = 48;
 /* The literal/length and distance codes of every block, one thread per tree: code rows and the block's cost.  The bit-length
- * tree and the header bits are k_huffman_hdr's.  (sinfo and blkhdr are not read.) */
+ * tree and the header bits are k_huffman_hdr's.  (Of sinfo only the block counts are read, blkhdr not at all.) */
+constexpr int HUFF_MAXSTREAMS = 512; /* streams of one lane: 4 planes x <= 128 chunks of a batch */
 __global__ __launch_bounds__(HUFF_TREES) void k_huffman(const StreamInfo *__restrict__ sinfo, uint32_t nstreams,
-                                                        const uint32_t *__restrict__ blkbase, const uint16_t *__restrict__ blkfreq,
+                                                        const uint16_t *__restrict__ blkfreq,
                                                         uint32_t *__restrict__ blkcode, uint32_t *__restrict__ blkhdr,
                                                         BlkMeta *__restrict__ meta,
                                                         unsigned long long *__restrict__ dbg /* NULL, or phase clocks: [i] max, [16 + i] sum, [32] trees */)
 {
     constexpr int HT = HUFF_TREES; /* (the macros above address the tree of this thread) */
     __shared__ TreeMem<HT> tm;
+    __shared__ uint32_t s_base[HUFF_MAXSTREAMS + 1]; /* blocks in the streams before s; [nstreams] = all blocks of the lane */
     const int tid = threadIdx.x;
     unsigned long long tp = dbg ? (unsigned long long)clock64() : 0ull;
 #define HPHASE(i)                                                              \
@@ -357,19 +331,57 @@ __global__ __launch_bounds__(HUFF_TREES) void k_huffman(const StreamInfo *__rest
             tp = now_;                                                         \
         }                                                                      \
     } while (0)
+    constexpr int NBLK_LOADS = (HUFF_MAXSTREAMS + HT - 1) / HT;
+    uint32_t nblk_of[NBLK_LOADS]; /* the lane's block counts, stream tid + HT r: all loads in one round trip (used below; under way meanwhile) */
+#pragma unroll
+    for (int r = 0; r < NBLK_LOADS; r++) {
+        const uint32_t i = (uint32_t)(tid + HT * r);
+        nblk_of[r] = i < nstreams ? sinfo[i].nblk : 0u;
+    }
     /* all-zero code lengths for every tree of the workgroup (one wave: cooperative, before anyone leaves) */
     for (int w = tid; w < HSLOTS * HT / 4; w += HT) reinterpret_cast<uint32_t *>(tm.leaflen)[w] = 0;
     __builtin_amdgcn_wave_barrier();
+    /* The trees are packed densely, 48 a wave, whatever stream they belong to: tree number -> (stream, block) needs the
+     * prefix sums of the streams' block counts.  Every workgroup makes them itself -- the counts in one round of
+     * independent loads, each thread the sum of its few consecutive streams, one scan over the threads -- which costs a
+     * microsecond in front of a tree's 450, and saves the single-workgroup launch that used to stand between the
+     * histograms and the trees of every lane. */
+#pragma unroll
+    for (int r = 0; r < NBLK_LOADS; r++) {
+        const uint32_t i = (uint32_t)(tid + HT * r);
+        if (i < nstreams) s_base[i] = nblk_of[r];
+    }
+    __builtin_amdgcn_wave_barrier();
+    {
+        const uint32_t per = (nstreams + HT - 1u) / HT, i0 = (uint32_t)tid * per;
+        uint32_t sum = 0;
+        for (uint32_t r = 0; r < per; r++)
+            if (i0 + r < nstreams) sum += s_base[i0 + r];
+        uint32_t inc = sum;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = (uint32_t)__shfl_up((int)inc, d);
+            if (tid >= d) inc += o;
+        }
+        uint32_t run = inc - sum;
+        for (uint32_t r = 0; r < per; r++) {
+            if (i0 + r >= nstreams) break;
+            const uint32_t v = s_base[i0 + r];
+            s_base[i0 + r] = run;
+            run += v;
+        }
+        if (tid == HT - 1) s_base[nstreams] = inc;
+    }
+    __builtin_amdgcn_wave_barrier();
     const uint32_t job = blockIdx.x * HT + tid;
-    const uint32_t total = blkbase[nstreams];
+    const uint32_t total = s_base[nstreams];
     if (job >= total) return;
     /* job -> (stream, block) */
     uint32_t lo = 0, hi = nstreams - 1;
     while (lo < hi) {
         const uint32_t mid = (lo + hi + 1) >> 1;
-        if (blkbase[mid] <= job) lo = mid; else hi = mid - 1;
+        if (s_base[mid] <= job) lo = mid; else hi = mid - 1;
     }
-    const uint32_t s = lo, b = job - blkbase[lo];
+    const uint32_t s = lo, b = job - s_base[lo];
     const uint16_t *fq = blkfreq + ((size_t)s * MAXBLK + b) * HROW;
     const uint4 *fq8 = reinterpret_cast<const uint4 *>(fq); /* 8 frequencies per load */
     uint32_t *code_out = blkcode + ((size_t)s * MAXBLK + b) * HROW;
@@ -547,10 +559,16 @@ __device__ __forceinline__ void stage_put(uint32_t *stage, uint32_t pos, uint32_
     if (sh + n > 32u && w + 1u < (uint32_t)HDRWORDS) atomicOr(&stage[w + 1u], v >> (32u - sh));
 }
 
-__global__ __launch_bounds__(64) void k_huffman_hdr(const StreamInfo *__restrict__ sinfo, uint32_t nstreams,
-                                                    const uint32_t *__restrict__ blkbase, const uint32_t *__restrict__ blkcode,
-                                                    uint32_t *__restrict__ blkhdr, BlkMeta *__restrict__ meta)
+__global__ __launch_bounds__(64) void k_huffman_hdr(const StreamInfo *__restrict__ sinfo, const uint32_t *__restrict__ blkcode,
+                                                    uint32_t *__restrict__ blkhdr, BlkMeta *__restrict__ meta,
+                                                    const uint16_t *__restrict__ pairhist, const TileInfo *__restrict__ tinfo,
+                                                    uint2 *__restrict__ pairbits)
 {
+    /* blockIdx.x < MAXBLK: the header of block blockIdx.x;  the SPS workgroups behind them: the pair bits of a segment */
+    if (blockIdx.x >= (uint32_t)MAXBLK) {
+        pair_bits_segment(blockIdx.x - (uint32_t)MAXBLK, blockIdx.y, sinfo, pairhist, blkcode, tinfo, pairbits);
+        return;
+    }
     constexpr int HT = 1; /* (the macros below address the tree of "thread" 0) */
     __shared__ TreeMem<HT> tm;
     __shared__ uint32_t stage[HDRWORDS];
@@ -558,14 +576,8 @@ __global__ __launch_bounds__(64) void k_huffman_hdr(const StreamInfo *__restrict
     __shared__ long s_opt;
     const int tid = 0;
     const int lane = threadIdx.x;
-    const uint32_t job = blockIdx.x;
-    if (job >= blkbase[nstreams]) return;
-    uint32_t lo = 0, hi = nstreams - 1;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if (blkbase[mid] <= job) lo = mid; else hi = mid - 1;
-    }
-    const uint32_t s = lo, b = job - blkbase[lo];
+    const uint32_t b = blockIdx.x, s = blockIdx.y;
+    if (b >= sinfo[s].nblk) return;
     const uint32_t *code = blkcode + ((size_t)s * MAXBLK + b) * HROW;
     /* the lanes' lengths: symbol 64 k + lane */
     uint32_t l[5];

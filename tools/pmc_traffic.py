@@ -33,8 +33,7 @@ out = {"source": f"rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE 
                  f"{passes} decompress passes, MI355X.  bytes_per_pass = (sum over all launches) / {passes}; FETCH_SIZE doubled for the kernels with 16-B-per-lane "
                  "streaming loads (fetch_factor 2), as reported for the others",
        "passes": passes, "kernels": {}}
-COMPRESS = {"k_tile_summary", "k_stream_scan", "k_histogram", "k_block_reduce", "k_block_index", "k_huffman", "k_huffman_hdr", "k_stream_layout", "k_pair_bits",
-            "k_pair_offsets", "k_container", "k_zero_records", "k_clear_boundaries", "k_emit", "k_emit_headers"}
+COMPRESS = {"k_tile_summary", "k_stream_scan", "k_histogram", "k_block_reduce", "k_huffman", "k_huffman_hdr", "k_stream_layout", "k_container", "k_zero_records", "k_clear_boundaries", "k_emit", "k_emit_headers"}
 tot = {"compress": 0, "decompress": 0}
 for k in sorted(set(fetch) | set(write)):
     if not k.startswith("k_"):
