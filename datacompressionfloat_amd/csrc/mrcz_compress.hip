@@ -382,7 +382,8 @@ __global__ __launch_bounds__(64 * W) void k_histogram(const uint8_t *__restrict_
             }
         }
         /* window-slide positions whose threshold lies in this tile (App. B.4): steady thresholds are
-         * 32768 apart, so at most one of them plus the final exhausted-state one can fall in a tile */
+         * 32768 apart, so at most one of them plus the final exhausted-state one can fall in a tile.  (A final threshold
+         * equal to n lies in no tile and is not written here: k_stream_layout knows that slide's position, n.) */
         if (nslide) {
             const uint32_t js = n >= 65536u ? n / 32768u - 1u : 0u;
             uint32_t cand[2];
@@ -597,7 +598,12 @@ __global__ __launch_bounds__(64) void k_stream_layout(StreamInfo *__restrict__ s
     StreamInfo si = sinfo[s];
     const int lane = lane_id();
     const uint32_t nslide = slide_count(si.n);
-    for (uint32_t i = lane; i <= nslide; i += 64) s_q[i] = i ? slideq[(size_t)s * MAXSLIDE + i] : 0u;
+    /* A stream whose window holds exactly 65274 bytes when the input ends (n = 65274 + 32768 j) makes its last slide at
+     * position n itself, behind the last token: k_histogram, which finds a slide in the tile that holds its threshold, has
+     * no tile for it and leaves slideq[nslide] as it was.  The position is n. */
+    const bool slide_at_end = nslide && slide_threshold(si.n, nslide) >= si.n;
+    for (uint32_t i = lane; i <= nslide; i += 64)
+        s_q[i] = !i ? 0u : (i == nslide && slide_at_end) ? si.n : slideq[(size_t)s * MAXSLIDE + i];
     __builtin_amdgcn_wave_barrier();
     constexpr int R = (MAXBLK + 63) / 64; /* consecutive blocks per lane */
     const uint32_t per = (si.nblk + 63u) / 64u; /* <= R */
