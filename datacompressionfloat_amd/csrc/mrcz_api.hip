@@ -350,12 +350,25 @@ static int ensure_planes(mrcz_ctx *ctx)
     return MRCZ_OK;
 }
 
+/* The byte planes that the first pass makes zero in every word past the file header (tile_cleared, mrcz_tile.h): known from the
+ * launch arguments alone, never from the data.  A mask clears plane j where its byte j is zero (-b 8: plane 0, -b 16: planes 0-1,
+ * ...), the "-s int" quantiser keeps the low byte only, abs_round clears nothing that could be told in advance. */
+static uint32_t cleared_planes(Xform xf, uint32_t mask)
+{
+    if (xf == Xform::Quant) return 0xeu;
+    if (xf == Xform::AbsErr) return 0u;
+    uint32_t set = 0;
+    for (int j = 0; j < 4; j++)
+        if (((mask >> (8 * j)) & 0xffu) == 0u) set |= 1u << j;
+    return set;
+}
+
 /* One half ("lane") of a compress batch: chunks [c_first, c_first + nb) of the batch, whose workspace rows start at
  * stream s0 = 4 * (chunks of the batch before this lane).  phase 0 = everything up to the sizes (summary ... pair
  * offsets), phase 1 = layout in the output + chunk headers, phase 2 = boundary words + emit.  The kernels index the workspace by the
  * lane-local stream number, so a lane is just a set of offset base pointers. */
 static int compress_lane(mrcz_ctx *ctx, hipStream_t lstream, int phase, int slot, uint32_t s0, const uint32_t *bin, uint64_t bfl,
-                         uint32_t nb, uint32_t mask, uint32_t fstart, uint8_t *out, Xform xf, AbsErr ae)
+                         uint32_t nb, uint32_t mask, uint32_t fstart, uint8_t *out, Xform xf, AbsErr ae, uint32_t cleared)
 {
     const uint32_t ns = 4u * nb;
     TileSum *tsum = ctx->tsum + (size_t)s0 * TPS;
@@ -373,13 +386,13 @@ static int compress_lane(mrcz_ctx *ctx, hipStream_t lstream, int phase, int slot
     uint32_t *pairoff = ctx->pairoff + (size_t)s0 * MAXPAIR;
     uint8_t *planes = ctx->planes + (size_t)s0 * CHK;
     if (phase == 0) {
-        if (xf == Xform::Quant) LAUNCH("k_tile_summary", k_tile_summary<Xform::Quant>, dim3(SPS, nb), dim3(256), bin, bfl, mask, fstart, tsum, planes);
-        else if (xf == Xform::AbsErr) LAUNCH("k_tile_summary", k_tile_summary<Xform::AbsErr>, dim3(SPS, nb), dim3(256), bin, bfl, ae, fstart, tsum, planes);
-        else LAUNCH("k_tile_summary", k_tile_summary<Xform::Mask>, dim3(SPS, nb), dim3(256), bin, bfl, mask, fstart, tsum, planes);
+        if (xf == Xform::Quant) LAUNCH("k_tile_summary", k_tile_summary<Xform::Quant>, dim3(SPS, nb), dim3(256), bin, bfl, mask, fstart, cleared, tsum, planes);
+        else if (xf == Xform::AbsErr) LAUNCH("k_tile_summary", k_tile_summary<Xform::AbsErr>, dim3(SPS, nb), dim3(256), bin, bfl, ae, fstart, cleared, tsum, planes);
+        else LAUNCH("k_tile_summary", k_tile_summary<Xform::Mask>, dim3(SPS, nb), dim3(256), bin, bfl, mask, fstart, cleared, tsum, planes);
         LAUNCH("k_stream_scan", k_stream_scan, dim3(ns), dim3(256), tsum, bfl, tinfo, sinfo, blkstart);
         /* waves per workgroup by batch size: 4 up to 12 chunks, else 1 */
-        if (nb <= 12u) LAUNCH("k_histogram", k_histogram<4>, dim3(SPS, nb, 4), dim3(256), planes, bfl, tinfo, pairhist, blkstart, slideq, HIST_FEW);
-        else LAUNCH("k_histogram", k_histogram<1>, dim3(SPS, nb, 4), dim3(64), planes, bfl, tinfo, pairhist, blkstart, slideq, HIST_FEW);
+        if (nb <= 12u) LAUNCH("k_histogram", k_histogram<4>, dim3(SPS, nb, 4), dim3(256), planes, bfl, tinfo, pairhist, blkstart, slideq, HIST_FEW, fstart, cleared);
+        else LAUNCH("k_histogram", k_histogram<1>, dim3(SPS, nb, 4), dim3(64), planes, bfl, tinfo, pairhist, blkstart, slideq, HIST_FEW, fstart, cleared);
         LAUNCH("k_block_reduce", k_block_reduce, dim3(MAXBLK, ns), dim3(64 * BR_WAVES), tinfo, sinfo, pairhist, blkfreq);
         HIPCHK(hipEventRecord(ctx->ev_stream[slot], lstream), "event"); /* this lane's streaming passes are done: the next lane may start */
         unsigned long long *hdbg = ctx->phase_profile == 3 ? ctx->dbgphase : (unsigned long long *)NULL; /* developer tool */
@@ -393,7 +406,7 @@ static int compress_lane(mrcz_ctx *ctx, hipStream_t lstream, int phase, int slot
         LAUNCH("k_container", k_container, dim3(1), dim3(256), sinfo, nb, out, ctx->result);
     } else {
         LAUNCH("k_clear_boundaries", k_clear_boundaries, dim3(MAXBLK + 1, ns), dim3(64), sinfo, lay, meta, pairoff, out);
-        LAUNCH("k_emit", k_emit, dim3(SPS, nb, 4), dim3(64), planes, bfl, tinfo, sinfo, lay, blkstart, blkcode, pairoff, out, ctx->result);
+        LAUNCH("k_emit", k_emit, dim3(SPS, nb, 4), dim3(64), planes, bfl, tinfo, sinfo, lay, blkstart, blkcode, pairoff, out, ctx->result, fstart, cleared);
         LAUNCH("k_emit_headers", k_emit_headers, dim3(MAXBLK + 1, ns), dim3(64), sinfo, lay, meta, blkhdr, blkstart, out);
     }
     return MRCZ_OK;
@@ -414,6 +427,7 @@ static int compress_enqueue(mrcz_ctx_t *ctx, const void *d_in, uint64_t nfloats,
     if (out_cap < bound) return fail(ctx, MRCZ_ECAP, "output capacity below mrcz_records_bound()", hipSuccess);
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
     const uint32_t mask = mask_of(bits);
+    const uint32_t cleared = cleared_planes(xf, mask);
     const uint64_t nchunks = (nfloats + CHK - 1) / CHK;
     const uint32_t *in = (const uint32_t *)d_in;
     uint8_t *out = (uint8_t *)d_out;
@@ -484,7 +498,7 @@ static int compress_enqueue(mrcz_ctx_t *ctx, const void *d_in, uint64_t nfloats,
                 }
                 const uint32_t row0 = 4u * cb; /* first workspace row (stream slot) of this lane: a chunk's rows are its place in the batch */
                 ctx->last_lc0[l] = cb; ctx->last_row0[l] = row0;
-                if (int rc = compress_lane(ctx, st, phase, (int)l, row0, in + c0 * CHK + f0, bfll, nbl, mask, fstart, out, xf, ae)) return rc;
+                if (int rc = compress_lane(ctx, st, phase, (int)l, row0, in + c0 * CHK + f0, bfll, nbl, mask, fstart, out, xf, ae, cleared)) return rc;
                 if (phase == 1) {
                     HIPCHK(hipEventRecord(ctx->ev_cont, st), "event");
                     cont_pending = true;

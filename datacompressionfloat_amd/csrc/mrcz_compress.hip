@@ -21,6 +21,8 @@
  *   k_clear_boundaries small   : zero the few words in which two writers meet (the output is not zero-filled)
  *   k_emit           N B x 4 read, Z B written : Huffman/stored/raw bit packing, whole words
  *   k_emit_headers   small     : block headers, END_BLOCK codes, sync markers
+ * A plane that the mask or the quantiser clears (tile_cleared, mrcz_tile.h) is neither written by the first pass nor read by the
+ * other two, but for tile 0 of a file's first chunk: N B less in each of the three per cleared plane.
  * No MFMA anywhere: the path is byte/bit manipulation bound by HBM and LDS.
  */
 #include "mrcz_tile.h"
@@ -33,7 +35,7 @@ namespace mrcz {
 template <Xform X>
 __global__ __launch_bounds__(256) void k_tile_summary(const uint32_t *__restrict__ in, uint64_t nfloats,
                                                       typename XformArg<X>::type mask, uint32_t first_chunk_is_file_start,
-                                                      TileSum *__restrict__ tsum, uint8_t *__restrict__ planes)
+                                                      uint32_t cleared, TileSum *__restrict__ tsum, uint8_t *__restrict__ planes)
 {
     __shared__ __attribute__((aligned(16))) uint8_t lds[4 * PLANE_LDS];
     const uint32_t g = blockIdx.x, c = blockIdx.y;
@@ -54,7 +56,10 @@ __global__ __launch_bounds__(256) void k_tile_summary(const uint32_t *__restrict
         const uint8_t *plane = lds + w * PLANE_LDS;
         uint32_t x[16];
         lane_row(plane, lane, x);
-        if (64 * lane < len) { /* the masked plane, for the later passes: stream s at planes + s * CHK, 64 B per lane */
+        /* the masked plane, for the later passes: stream s at planes + s * CHK, 64 B per lane.  A cleared tile (mrcz_tile.h) is
+         * not stored: the later passes know it is zero */
+        const bool zero_tile = tile_cleared(cleared, w, t0, unmasked); /* (a cross-lane read: asked by the whole wave) */
+        if (!zero_tile && 64 * lane < len) {
             uint4 *dst = reinterpret_cast<uint4 *>(planes + (size_t)s * CHK + t0 + 64u * (uint32_t)lane);
 #pragma unroll
             for (int k = 0; k < 4; k++) dst[k] = make_uint4(x[4 * k], x[4 * k + 1], x[4 * k + 2], x[4 * k + 3]);
@@ -300,10 +305,11 @@ __device__ __forceinline__ int token_boundary_at(const LaneTile &lt, const LaneC
     return p - m + l;
 }
 
-/* the lane's 64 consecutive plane bytes of tile t0 (zeros past the end of the chunk), straight from the plane in HBM */
-__device__ __forceinline__ void load_plane_row(const uint8_t *__restrict__ pl, uint32_t t0, int len, int lane, uint32_t x[16])
+/* the lane's 64 consecutive plane bytes of tile t0 (zeros past the end of the chunk), straight from the plane in HBM; a cleared
+ * tile (tile_cleared, wave-uniform) is zeros without a load: pass 1 did not store it */
+__device__ __forceinline__ void load_plane_row(const uint8_t *__restrict__ pl, uint32_t t0, int len, int lane, bool cleared, uint32_t x[16])
 {
-    if (64 * lane < len) {
+    if (!cleared && 64 * lane < len) {
         const uint4 *src = reinterpret_cast<const uint4 *>(pl + t0 + 64u * (uint32_t)lane);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -338,7 +344,8 @@ __device__ __forceinline__ uint64_t bytes_equal_mask(const uint32_t x[16], uint3
 template <int W>
 __global__ __launch_bounds__(64 * W) void k_histogram(const uint8_t *__restrict__ planes, uint64_t nfloats,
                                                   const TileInfo *__restrict__ tinfo, uint16_t *__restrict__ pairhist,
-                                                  uint32_t *__restrict__ blkstart, uint32_t *__restrict__ slideq, uint32_t few_thr)
+                                                  uint32_t *__restrict__ blkstart, uint32_t *__restrict__ slideq, uint32_t few_thr,
+                                                  uint32_t first_chunk_is_file_start, uint32_t cleared)
 {
     /* one workgroup = one (segment, plane), its W waves take the segment's tiles in turn.  A tile knows its block from its
      * symbol prefix (TileInfo::P), and a segment's 32768 positions touch at most three blocks: one LDS row per block, all
@@ -353,6 +360,7 @@ __global__ __launch_bounds__(64 * W) void k_histogram(const uint8_t *__restrict_
     const int lane = lane_id(), wv = (int)(threadIdx.x >> 6), w = plane_of_slot(blockIdx.z);
     const uint32_t s = 4u * c + (uint32_t)w;
     const uint8_t *pl = planes + (size_t)s * CHK;
+    const uint32_t unmasked = (c == 0 && first_chunk_is_file_start) ? 256u : 0u;
     for (int i = (int)threadIdx.x; i < 4 * HROW; i += 64 * W) rows[i] = 0;
     const uint32_t blk0 = tinfo[(size_t)s * TPS + (g * SEG) / TILE].P / BLK_SYMS;
     if (W > 1) __syncthreads(); else __builtin_amdgcn_wave_barrier();
@@ -366,7 +374,7 @@ __global__ __launch_bounds__(64 * W) void k_histogram(const uint8_t *__restrict_
         const uint32_t curBlk = tinf.P / BLK_SYMS;
         uint32_t *rowA = rows + (curBlk - blk0) * HROW, *rowB = rowA + HROW;
         uint32_t x[16];
-        load_plane_row(pl, t0, len, lane, x);
+        load_plane_row(pl, t0, len, lane, tile_cleared(cleared, w, t0, unmasked), x);
         const LaneTile lt = analyse_lane(x, lane, len, tinf.B, tinf.F);
         const LaneCls cls = classify_lane(lt.E, lt.a, lt.prevS, lt.nextS);
         const uint64_t S = cls.S & lt.V, M = cls.M & lt.V;
@@ -1046,7 +1054,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))
                                               const StreamInfo *__restrict__ sinfo, const BlkLay *__restrict__ lay,
                                               const uint32_t *__restrict__ blkstart, const uint32_t *__restrict__ blkcode,
                                               const uint32_t *__restrict__ pairoff, uint8_t *__restrict__ out,
-                                              uint64_t *__restrict__ result /* [8] += tile parts cut in two (mrcz_debug_emit_splits) */)
+                                              uint64_t *__restrict__ result /* [8] += tile parts cut in two (mrcz_debug_emit_splits) */,
+                                              uint32_t first_chunk_is_file_start, uint32_t cleared)
 {
     /* one wave = one (segment, plane): no workgroup barriers, light planes retire early.  The lane's 64 plane bytes stay in
      * registers for both passes: an LDS copy of the tile costs 5 KB per wave and with it a third of the occupancy, and this
@@ -1060,6 +1069,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))
     const int lane = lane_id(), w = plane_of_slot(blockIdx.z);
     const uint32_t s = 4u * c + (uint32_t)w;
     const uint8_t *pl = planes + (size_t)s * CHK;
+    const uint32_t unmasked = (c == 0 && first_chunk_is_file_start) ? 256u : 0u;
     const StreamInfo si = sinfo[s];
     uint32_t *out32 = reinterpret_cast<uint32_t *>(out);
     const uint64_t paybit = si.payoff * 8ull;
@@ -1083,7 +1093,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))
         if (t0 >= n) break;
         const int len = (int)((n - t0) < (uint32_t)TILE ? (n - t0) : (uint32_t)TILE);
         uint32_t x[16];
-        load_plane_row(pl, t0, len, lane, x);
+        const bool zero_tile = tile_cleared(cleared, w, t0, unmasked); /* the plane in HBM holds nothing of this tile */
+        load_plane_row(pl, t0, len, lane, zero_tile, x);
         if (si.raw) {
             /* RAW plane (zip.c:184-190): the payload is the plane itself.  Each lane stores its own 64 bytes with four
              * 16-byte stores at whatever alignment the payload has (gfx9 global memory takes unaligned accesses);
@@ -1097,7 +1108,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))
                     __builtin_memcpy(dst + 16 * k, &v, 16);
                 }
             } else {
-                for (int i = 0; i < mine; i++) dst[i] = pl[t0 + 64u * (uint32_t)lane + (uint32_t)i];
+                for (int i = 0; i < mine; i++) dst[i] = zero_tile ? (uint8_t)0 : pl[t0 + 64u * (uint32_t)lane + (uint32_t)i];
             }
             continue;
         }
@@ -1150,7 +1161,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))
             if (mode == 0) {
                 /* STORED block: plane bytes [pos0, pos1) go out verbatim at a byte-aligned address.  The wave assembles
                  * aligned output dwords from the plane in HBM (the tile was just read: cache hits; stored blocks are only the
-                 * first and last block of an incompressible plane); a partial first / last dword goes out byte by byte. */
+                 * first and last block of an incompressible plane); a partial first / last dword goes out byte by byte.  The
+                 * part lies in one tile: of a cleared one its bytes are zeros, not loads. */
                 const uint32_t nbytes = (uint32_t)(pos1 - pos0);
                 const uint64_t dg = si.payoff + (cur >> 3);       /* cur is a multiple of 8 here */
                 const uint32_t mis = (uint32_t)(dg & 3u);
@@ -1163,7 +1175,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EMIT_WAVES))
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
                         const int rel = (int)(4u * k + (uint32_t)j) - (int)mis; /* byte of the part */
-                        if (rel >= 0 && rel < (int)nbytes) v |= (uint32_t)src[rel] << (8 * j);
+                        if (rel >= 0 && rel < (int)nbytes) v |= zero_tile ? 0u : (uint32_t)src[rel] << (8 * j);
                         else full = false;
                     }
                     if (full) out32[w0 + k] = v;

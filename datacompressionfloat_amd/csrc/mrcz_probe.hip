@@ -132,6 +132,7 @@ static int probe_enqueue(mrcz_ctx *ctx, const void *d_in, uint64_t nfloats, uint
     if (!(eps_abs >= 0.0)) eps_abs = INFINITY;
     if (!(eps_rel >= 0.0)) eps_rel = INFINITY;
     const Xform xf = xform == MRCZ_PROBE_INT8 ? Xform::Quant : xform == MRCZ_PROBE_ABS ? Xform::AbsErr : Xform::Mask;
+    const uint32_t cleared = cleared_planes(xf, mask);
     const uint32_t *in = (const uint32_t *)d_in;
     const uint64_t nchunks = (nfloats + CHK - 1) / CHK;
     hipStream_t lstream = ctx->stream;
@@ -142,7 +143,7 @@ static int probe_enqueue(mrcz_ctx *ctx, const void *d_in, uint64_t nfloats, uint
         const uint32_t fstart = (first_chunk + c0 == 0) ? 1u : 0u;
         const uint32_t *bin = in + c0 * CHK;
         /* the whole batch as one lane on the compute stream: workspace rows 0 .. 4 nb - 1, sizes only (no output pointer is used) */
-        if (int rc = compress_lane(ctx, lstream, 0, 0, 0u, bin, bfl, nb, mask, fstart, (uint8_t *)NULL, xf, ae)) return rc;
+        if (int rc = compress_lane(ctx, lstream, 0, 0, 0u, bin, bfl, nb, mask, fstart, (uint8_t *)NULL, xf, ae, cleared)) return rc;
         LAUNCH("k_probe_sizes", k_probe_sizes, dim3(1), dim3(256), ctx->sinfo, nb, ctx->result);
         if (!d_acc) continue;
         const uint64_t bbase = (first_chunk + c0) * (uint64_t)CHK;

@@ -65,6 +65,18 @@ enum class Xform { Mask, Quant, AbsErr };
 template <Xform X> struct XformArg { typedef uint32_t type; }; /* Mask: the mask (Quant: unused) */
 template <> struct XformArg<Xform::AbsErr> { typedef AbsErr type; };
 
+/* Cleared planes.  The host knows before the first launch which byte planes the transform makes zero in every word past the
+ * file header (cleared_planes, mrcz_api.hip): bit j of `cleared` <=> plane j.  A tile of such a plane that lies wholly at or
+ * past `unmasked_below` (every tile but tile 0 of a file's first chunk: 256 < TILE) is zero by construction, and no pass goes
+ * to HBM for it: k_tile_summary does not store its rows, k_histogram and k_emit take them as zeros.  The workspace is reused
+ * from call to call and by the decoder, so such rows hold stale bytes, and the rule that holds everywhere is:
+ *     no kernel reads a plane byte that pass 1 of the same call did not store.
+ * t0 = chunk-relative start of the tile.  Wave-uniform (a scalar branch): `plane` must be the same in every lane of the wave. */
+__device__ __forceinline__ bool tile_cleared(uint32_t cleared, int plane, uint32_t t0, uint32_t unmasked_below)
+{
+    return __builtin_amdgcn_readfirstlane((int)((cleared >> plane) & 1u)) != 0 && t0 >= unmasked_below;
+}
+
 /* All 256 threads: stage tile [t0, t0+len) of one chunk into lds[4][PLANE_LDS].
  * cin = first word of the chunk; positions below `unmasked_below` (256 for chunk 0 of a file,
  * workers.c:90-94) keep all their bits. */
